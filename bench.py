@@ -2,6 +2,7 @@
 """Headline benchmark: Mpoints/s of k-th-NN distance (k=100) on 1B uniform float3.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--points P] [--k K] [--variant V]
+                    [--full] [--dump-outputs DIR]
 
 Launched by the driver as ``torch.distributed.run --nproc-per-node N bench.py --gpus N``
 for N > 1 (one rank per GPU, RCCL over xGMI; bootstrap through parallel/launch.init:
@@ -18,11 +19,16 @@ Pipelined (--pipeline; default for the unordered halo pipeline on GPUs from 1e7
 points): a stream of point sets — two different synthetic sets alternate step by step, and while
 step i runs its k-NN on the compute stream, step i+1's points are copied host -> device
 (PCIe H2D does not compete with the VALU-bound k-NN). Every step still uploads, builds, queries and
-returns its whole set; the first set's upload is inside the timed region, and both sets'
-last outputs are verified. ms_per_step is then the per-set time of the stream.
+returns its whole set; the first set's upload is inside the timed region, and (--full) both
+sets' last outputs are verified. ms_per_step is then the per-set time of the stream.
 
-After the timed region (untimed): a brute-force check of 256 sampled outputs per verified
-set against all points (utils/verify.py, `sampled_exact`); the SINGLE-SET LATENCY — one
+A plain run sets up, warms up, times the K steps, writes the last timed step's distances
+when --dump-outputs DIR is given (DIR/distances.npy, float32; a fixed seeded sample above
+2^22 points; the inputs depend on the arguments only, so two builds can be compared output
+for output) and prints the JSON line. Everything else runs with --full only.
+
+--full, after the timed region (untimed): the all-finite scan and a brute-force check of
+256 sampled outputs per verified set against all points (utils/verify.py, `sampled_exact`); the SINGLE-SET LATENCY — one
 set from pinned host memory through H2D, index build, k-NN and results back in host
 memory, nothing overlapped with another set (the BASELINE.md clock for one problem; best
 of two runs, max over ranks; `single_set_ms` / `single_set_mpts`); and one instrumented
@@ -144,7 +150,16 @@ def parse():
                          "is streamed under the redistribution); -1 (default) = 1 for the unordered "
                          "halo pipeline on GPUs from 1e7 points")
     ap.add_argument("--verify", type=int, default=256,
-                    help="sampled outputs checked by brute force after the timed region (0 = off)")
+                    help="with --full: sampled outputs checked by brute force after the timed region "
+                         "(0 = off)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything the headline figure does not need: "
+                         "the all-finite scan and the sampled brute-force check of the outputs, the "
+                         "single-set latency and one instrumented step (per-phase times, exchange sizes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the distances the last timed step returned to "
+                         "DIR/distances.npy (float32; a fixed seeded sample of DUMP_SAMPLE outputs when "
+                         "there are more; on several ranks DIR/distances_rank<r>of<P>.npy per rank)")
     return ap.parse_args()
 
 
@@ -180,6 +195,31 @@ def make_points(n_total: int, rank: int, size: int, device, variant: str, datase
 def _sync(device):
     if device.type == "cuda":
         torch.cuda.synchronize(device)
+
+
+DUMP_SAMPLE = 1 << 22  # --dump-outputs: outputs kept of a larger result (16 MB of float32)
+DUMP_SEED = 4321
+
+
+def dump_outputs(path_dir: str, out_h: torch.Tensor, n_total: int, rank: int, world: int) -> str:
+    """--dump-outputs: this rank's share of the last timed step's distances as one .npy
+    (float32). Up to DUMP_SAMPLE points everything is written; above, the outputs of
+    DUMP_SAMPLE global point ids drawn once from a fixed seed (sorted, so the same ids for
+    every rank count and every run)."""
+    import numpy as np
+
+    b, e = block_range(n_total, rank, world)
+    if n_total <= DUMP_SAMPLE:
+        arr = out_h
+    else:
+        g = torch.Generator().manual_seed(DUMP_SEED)
+        ids = torch.randint(0, n_total, (DUMP_SAMPLE,), generator=g).sort().values
+        arr = out_h[ids[(ids >= b) & (ids < e)] - b]
+    os.makedirs(path_dir, exist_ok=True)
+    name = "distances.npy" if world == 1 else f"distances_rank{rank}of{world}.npy"
+    path = os.path.join(path_dir, name)
+    np.save(path, arr.to(torch.float32).contiguous().numpy())
+    return path
 
 
 def self_launch(args) -> int | None:
@@ -367,14 +407,20 @@ def main():
         heavy_unrefined = E.captured_heavy_cells(clear=True) or heavy_unrefined
     # the sets the timed steps wrote last (pipelined: both sets when K >= 2)
     written = sorted({(args.steps - 1 - j) % len(host_sets) for j in range(min(args.steps, len(host_sets)))})
-    finite_t = torch.tensor([sum(0 if host_outs[d].numel() == 0 or bool(torch.isfinite(host_outs[d]).all()) else 1
-                                 for d in written)], dtype=torch.int64, device=device)
-    comm.allreduce_(finite_t, "sum")
-    finite = int(finite_t.item()) == 0
+    if args.dump_outputs:
+        # the distances of the last timed step, before anything below runs another step
+        dump_outputs(args.dump_outputs, host_outs[(args.steps - 1) % len(host_sets)], n_total, rank, world)
 
-    # ---- untimed: sampled brute-force check of the timed result, then one instrumented step
+    # ---- untimed, --full only: all-finite scan and sampled brute-force check of the timed
+    # result, the single-set latency, then one instrumented step
+    finite = None
+    if args.full:
+        finite_t = torch.tensor([sum(0 if host_outs[d].numel() == 0 or bool(torch.isfinite(host_outs[d]).all())
+                                     else 1 for d in written)], dtype=torch.int64, device=device)
+        comm.allreduce_(finite_t, "sum")
+        finite = int(finite_t.item()) == 0
     check = None
-    if args.verify > 0:
+    if args.full and args.verify > 0:
         # (prePartitioned: rank r's file is the block [b, e) of global ids too — the check
         # counts every sampled id's distances over all ranks' points)
         b, _ = block_range(n_total, rank, world)
@@ -387,7 +433,7 @@ def main():
     # single-set latency: one set from pinned host memory to distances in host memory
     # (the default non-streamed path of this variant), best of two, max over ranks
     single_s = None
-    if args.mode == "halo" and device.type == "cuda":
+    if args.full and args.mode == "halo" and device.type == "cuda":
         best = math.inf
         for _ in range(2):
             comm.barrier()
@@ -401,13 +447,16 @@ def main():
         single_s = float(tt.item())
     # the instrumented step takes the timed path: pipelined steps start from points already
     # on the device (their upload ran under the previous step), so this one does too
-    pts_dev = host_pts.to(device) if pipelined else None
-    _sync(device)
-    detail = instrumented_detail(comm, lambda: (_step(phases=True, pts_in=pts_dev), _sync(device)),
-                                 lambda: info_last)
-    del pts_dev
+    detail = {}
+    if args.full:
+        pts_dev = host_pts.to(device) if pipelined else None
+        _sync(device)
+        detail = instrumented_detail(comm, lambda: (_step(phases=True, pts_in=pts_dev), _sync(device)),
+                                     lambda: info_last)
+        del pts_dev
     if rank == 0:
-        if args.phases or args.stats:
+        # (the stream of sets keeps no per-step record: its phases come from --full's step)
+        if (args.phases or args.stats) and info_last is not None:
             print(json.dumps({"phases_s": info_last.timer.times, "counts": info_last.plain_counts(),
                               "knn_stats": info_last.stats.counters}), file=sys.stderr)
         rec = {
@@ -417,6 +466,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(ms, 3),
             "higher_is_better": True,
             "scaling": "strong",

@@ -12,8 +12,9 @@ tear the other ranks down; a rank-count mismatch throws the same way
   when no progress was made for ``LSKNN_TIMEOUT`` seconds (default 900), it prints
   ``#r/P: ...`` to stderr and ends the process with ``os._exit`` (exit code 3 for a
   peer abort, 124 for a timeout) — no rank is ever left blocked in a collective. The
-  collective timeout of the process group is set to the same value, and RCCL's async
-  error handling is enabled, as a second line;
+  collective timeout of the process group is set ``COLLECTIVE_MARGIN_S`` later (so the
+  watchdog, which names the collective, is the one that fires), and RCCL's async error
+  handling is enabled, as a second line;
 * **fault injection** for tests — ``LSKNN_FAULT="rank=R,op=OP[,call=N][,kind=K]"``
   makes rank R fail its N-th (0-based, default 0) call of Comm method OP
   (``allreduce_``, ``allgather``, ``alltoallv``, ``p2p``, ``barrier``, ``allgather_host``
@@ -34,6 +35,7 @@ ABORT_KEY = "lsknn/abort"
 EXIT_PEER_ABORT = 3
 EXIT_TIMEOUT = 124
 EXIT_COMM_ERROR = 5  # the communicator reported an asynchronous error
+COLLECTIVE_MARGIN_S = 10.0  # the process group's own timeout comes this long after the watchdog's
 
 
 class InjectedFault(RuntimeError):

@@ -143,9 +143,11 @@ def init(device_pref: str = "auto", gpu_affinity: int = 0, verbose: bool = False
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29511")
         os.environ["RANK"], os.environ["WORLD_SIZE"] = str(rank), str(size)
-        # collective timeout = watchdog timeout; RCCL errors surface asynchronously
+        # collective timeout = watchdog timeout + a margin: with equal limits the group's own
+        # timeout (an error that does not name the collective) raced the watchdog's
+        # "timeout in <op>" on the waiting rank; RCCL errors surface asynchronously
         os.environ.setdefault("TORCH_NCCL_ASYNC_ERROR_HANDLING", "1")
-        timeout = datetime.timedelta(seconds=F.timeout_s())
+        timeout = datetime.timedelta(seconds=F.timeout_s() + F.COLLECTIVE_MARGIN_S)
         chosen = os.environ.get("LSKNN_DIST_BACKEND")
         backend = chosen or (default_gpu_backend() if use_gpu else "gloo")
         if backend not in ("nccl", "gloo", "rccl", "mpi"):

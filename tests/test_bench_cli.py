@@ -31,7 +31,7 @@ def _env():
 
 
 def test_bench_single_rank_cpu():
-    out = subprocess.run([sys.executable, "bench.py", "--device", "cpu", "--points", "20000", "--k", "8",
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--device", "cpu", "--points", "20000", "--k", "8",
                           "--steps", "2", "--warmup", "1"], cwd=ROOT, env=_env(), capture_output=True,
                          text=True, timeout=300)
     assert out.returncode == 0, out.stderr
@@ -50,7 +50,7 @@ def test_bench_single_rank_cpu():
 def test_bench_single_gpu_graph_and_eager(graph):
     """The driver's default single-GPU bench path: the step captured as a HIP graph (or
     eager), distances finite, the graph flag reported."""
-    out = subprocess.run([sys.executable, "bench.py", "--points", "300000", "--steps", "3", "--warmup", "1",
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--points", "300000", "--steps", "3", "--warmup", "1",
                           "--graph", graph, "--pipeline", "0"], cwd=ROOT, env=_env(), capture_output=True, text=True,
                          timeout=300)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -68,7 +68,7 @@ def test_bench_single_gpu_graph_and_eager(graph):
 def test_bench_single_gpu_pipelined():
     """The single-GPU bench as a stream of two alternating point sets, step i+1's
     upload under step i's k-NN; both sets' outputs of the last two steps are checked."""
-    out = subprocess.run([sys.executable, "bench.py", "--points", "300000", "--steps", "3", "--warmup", "1",
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--points", "300000", "--steps", "3", "--warmup", "1",
                           "--pipeline", "1"],  # (the default turns the stream on from 1e7 points)
                          cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -85,7 +85,7 @@ def test_bench_pipelined_forced_rccl_single_gpu():
     """--pipeline 1 on the multi-rank path (1-rank RCCL group): device-resident input per
     step, plain (non-streamed) redistribution beside the previous set's k-NN, both sets
     exact."""
-    out = subprocess.run([sys.executable, "bench.py", "--points", "300000", "--steps", "2", "--warmup", "1",
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--points", "300000", "--steps", "2", "--warmup", "1",
                           "--force-dist", "--pipeline", "1"],
                          cwd=ROOT, env=dict(_env(), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port())),
                          capture_output=True, text=True, timeout=300)
@@ -101,7 +101,7 @@ def test_bench_forced_rccl_single_gpu(backend):
     """One rank through the multi-rank pipeline on a real 1-rank RCCL group: every
     collective of the step (all-reduce, all-gather, all-to-all-v) runs on RCCL — through
     torch.distributed ("nccl") or the native communicator ("rccl", parallel/rccl.py)."""
-    out = subprocess.run([sys.executable, "bench.py", "--points", "300000", "--steps", "2", "--warmup", "1",
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--points", "300000", "--steps", "2", "--warmup", "1",
                           "--force-dist", "--pipeline", "0"], cwd=ROOT, env=dict(_env(), MASTER_ADDR="127.0.0.1",
                                                                MASTER_PORT=str(_free_port()),
                                                                LSKNN_DIST_BACKEND=backend),
@@ -127,7 +127,7 @@ def test_bench_default_backend_single_gpu(lib):
     env.pop("LSKNN_DIST_BACKEND", None)
     if lib == "broken":
         env["LSKNN_RCCL_LIB"] = os.path.join(ROOT, "bench.py")
-    out = subprocess.run([sys.executable, "bench.py", "--points", "300000", "--steps", "2", "--warmup", "1",
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--points", "300000", "--steps", "2", "--warmup", "1",
                           "--force-dist", "--pipeline", "0"], cwd=ROOT, env=env, capture_output=True, text=True,
                          timeout=300)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -142,7 +142,7 @@ def test_bench_default_backend_single_gpu(lib):
 @pytest.mark.parametrize("variant", ["unordered", "prepartitioned"])
 def test_bench_two_ranks_torchrun_gloo(variant):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2",
+           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--full", "--gpus", "2",
            "--device", "cpu", "--points", "30000", "--k", "16", "--steps", "2", "--warmup", "1",
            "--variant", variant]
     out = subprocess.run(cmd, cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=300)
@@ -176,7 +176,7 @@ def test_bench_four_ranks_streamed_uneven_chunks():
     7500 or 7501 points, i.e. one or two chunks — the agreed chunk count keeps their
     collective sequences equal; all sampled outputs exact."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4",
-           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "4",
+           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--full", "--gpus", "4",
            "--device", "cpu", "--points", "30001", "--k", "12", "--steps", "1", "--warmup", "1"]
     env = dict(_env(), LSKNN_FORCE_STREAM="1", LSKNN_STREAM_CHUNK="7500")
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
@@ -193,7 +193,7 @@ def test_bench_two_gpu_ranks_pipelined_gloo():
     stream, both ranks on the one GPU of the box over a host-staged gloo group (RCCL
     refuses two ranks on one device): both sets' sampled outputs exact."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2",
+           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--full", "--gpus", "2",
            "--points", "400000", "--steps", "3", "--warmup", "1", "--pipeline", "1"]
     out = subprocess.run(cmd, cwd=ROOT, env=dict(_env(), LSKNN_DIST_BACKEND="gloo"), capture_output=True,
                          text=True, timeout=300)
@@ -211,7 +211,7 @@ def test_bench_self_launches_gpus_ranks_on_cpu():
     env = _env()
     for v in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(v, None)
-    out = subprocess.run([sys.executable, "bench.py", "--gpus", "4", "--device", "cpu", "--points", "3e4",
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--gpus", "4", "--device", "cpu", "--points", "3e4",
                           "--steps", "2", "--warmup", "1"], cwd=ROOT, env=env, capture_output=True,
                          text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -241,7 +241,7 @@ def test_bench_self_launch_two_ranks_one_gpu_gloo():
     env["LSKNN_DIST_BACKEND"] = "gloo"
     for v in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(v, None)
-    out = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--points", "4e5", "--steps", "2",
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--gpus", "2", "--points", "4e5", "--steps", "2",
                           "--warmup", "1"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = _json_line(out.stdout)
@@ -306,12 +306,12 @@ def test_bench_eight_ranks_driver_shape_on_cpu():
     and every sampled output exact (VERDICT r5 next #4)."""
     pts = 40000
     torchrun = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
-                "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "8",
+                "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--full", "--gpus", "8",
                 "--device", "cpu", "--points", str(pts), "--k", "16", "--steps", "2", "--warmup", "1"]
     self_env = _env()
     for v in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         self_env.pop(v, None)
-    selfl = [sys.executable, "bench.py", "--gpus", "8", "--device", "cpu", "--points", str(pts), "--k", "16",
+    selfl = [sys.executable, "bench.py", "--full", "--gpus", "8", "--device", "cpu", "--points", str(pts), "--k", "16",
              "--steps", "2", "--warmup", "1"]
     for cmd, env in ((torchrun, dict(_env(), OMP_NUM_THREADS="1")), (selfl, dict(self_env, OMP_NUM_THREADS="1"))):
         out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
@@ -325,3 +325,106 @@ def test_bench_eight_ranks_driver_shape_on_cpu():
         own = rec["detail"]["owned_points_per_rank"]
         assert len(own) == 8 and sum(own) == pts
         assert rec["config"]["all_finite"] is True
+
+
+def _oracle(pts, k):
+    import math
+
+    from mpi_cuda_largescaleknn_amd.ops import kernels as K
+
+    return K.finalize_distances(K.kth_cpu(pts, pts, k, math.inf)).numpy()
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path, monkeypatch):
+    """A plain run times its steps and prints the headline fields only: no check, no
+    single-set latency, no instrumented step (those are --full's). --dump-outputs writes the
+    last timed step's distances: the same file with and without --full, equal to the CPU
+    oracle on the benchmark's own (seeded) points."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+
+    n, k = 20000, 8
+    recs, dumps = [], []
+    for i, extra in enumerate(([], ["--full"])):
+        d = tmp_path / f"dump{i}"
+        out = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--device", "cpu", "--points", str(n),
+                              "--k", str(k), "--steps", "2", "--warmup", "1", "--dump-outputs", str(d), *extra],
+                             cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-3000:]
+        recs.append(_json_line(out.stdout))
+        assert sorted(p.name for p in d.iterdir()) == ["distances.npy"]
+        dumps.append(np.load(d / "distances.npy"))
+    plain, full = recs
+    for rec in recs:
+        assert rec["steps"] == 2 and rec["warmup"] == 1 and rec["ms_per_step"] > 0
+        assert rec["unit"] == "Mpoints/s" and rec["dtype"] == "fp32" and rec["higher_is_better"] is True
+        # value and ms_per_step are the same clock: Mpoints/s = points / (ms_per_step * 1e3)
+        assert rec["value"] == pytest.approx(n / rec["ms_per_step"] / 1e3, rel=1e-2)
+    assert plain["metric"] == full["metric"]
+    assert plain["full"] is False and full["full"] is True
+    assert plain["config"]["sampled_exact"] is None and plain["config"]["all_finite"] is None
+    assert plain["single_set_ms"] is None and "phase_ms_max_over_ranks" not in plain["detail"]
+    assert full["config"]["sampled_exact"] == "256/256" and full["config"]["all_finite"] is True
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (n,)
+    assert np.array_equal(dumps[0], dumps[1])
+    monkeypatch.setattr(bench, "GEN_CHUNK", 1 << 24)  # (another test of this module shrinks it)
+    pts = bench.make_points(n, 0, 1, torch.device("cpu"), "unordered")
+    assert np.array_equal(dumps[0], _oracle(pts, k))
+
+
+def test_bench_dump_sample_is_fixed_and_rank_count_independent(tmp_path, monkeypatch):
+    """Above DUMP_SAMPLE outputs the dump is a fixed seeded sample of global point ids: the
+    same from call to call, and the ranks' files together hold what one rank's file holds."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+
+    n = 10007
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 500)
+    out = torch.arange(n, dtype=torch.float32) * 0.5
+    one = np.load(bench.dump_outputs(str(tmp_path / "a"), out, n, 0, 1))
+    again = np.load(bench.dump_outputs(str(tmp_path / "b"), out, n, 0, 1))
+    assert one.dtype == np.float32 and one.shape == (500,) and np.array_equal(one, again)
+    assert len(np.unique(one)) > 400 and one.min() >= 0 and one.max() <= (n - 1) * 0.5
+    parts = []
+    for r in range(3):
+        b, e = bench.block_range(n, r, 3)
+        path = bench.dump_outputs(str(tmp_path / "c"), out[b:e], n, r, 3)
+        assert os.path.basename(path) == f"distances_rank{r}of3.npy"
+        parts.append(np.load(path))
+    assert np.array_equal(np.concatenate(parts), one)
+    # at or below DUMP_SAMPLE outputs: everything
+    small = np.load(bench.dump_outputs(str(tmp_path / "d"), out[:500], 500, 0, 1))
+    assert np.array_equal(small, out[:500].numpy())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("pipeline,steps", [("0", 3), ("1", 2)])
+def test_bench_single_gpu_plain_run_dumps_last_step(tmp_path, monkeypatch, pipeline, steps):
+    """The plain single-GPU run (HIP graph, or the stream of two alternating sets whose
+    last timed step is then the second set): --dump-outputs holds that step's distances,
+    equal bit for bit to the CPU oracle on the same seeded points; nothing of --full ran."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+
+    n, k = 60000, 16
+    out = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--points", str(n), "--k", str(k), "--steps",
+                          str(steps), "--warmup", "1", "--pipeline", pipeline, "--dump-outputs", str(tmp_path)],
+                         cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-3000:]
+    rec = _json_line(out.stdout)
+    assert rec["steps"] == steps and rec["ms_per_step"] > 0 and rec["value"] > 0
+    assert rec["config"]["pipelined"] is (pipeline == "1") and rec["config"]["hip_graph"] is (pipeline == "0")
+    assert rec["config"]["sampled_exact"] is None and rec["single_set_ms"] is None
+    assert "phase_ms_max_over_ranks" not in rec["detail"]
+    got = np.load(tmp_path / "distances.npy")
+    assert got.dtype == np.float32 and got.shape == (n,)
+    monkeypatch.setattr(bench, "GEN_CHUNK", 1 << 24)  # (another test of this module shrinks it)
+    pts = bench.make_points(n, 0, 1, torch.device("cuda", 0), "unordered", dataset=(steps - 1) % 2
+                            if pipeline == "1" else 0)
+    assert np.array_equal(got, _oracle(pts, k))
