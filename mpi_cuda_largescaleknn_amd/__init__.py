@@ -38,4 +38,5 @@ def _hw_queues() -> None:
 
 _hw_queues()
 
-from .models.knn_engine import KnnConfig, build_index, knn_distances, query  # noqa: F401
+from .models.knn_engine import (KnnConfig, build_index, knn_distances, knn_query_distances, query,  # noqa: F401
+                                query_points)

@@ -58,7 +58,7 @@ class TreeView(C.Structure):
     ]
 
 
-HIP_ABI = 10  # lsk_hip_abi_version() of a library matching the structs below
+HIP_ABI = 11  # lsk_hip_abi_version() of a library matching the structs below
 
 
 class KnnArgs(C.Structure):
@@ -91,6 +91,9 @@ class KnnArgs(C.Structure):
         ("ngroups_dev", vp),
         ("wq", vp),
         ("qrot", vp),
+        ("qbucket", vp),
+        ("foreign", C.c_int32),
+        ("pad3", C.c_int32),
     ]
 
 
@@ -175,6 +178,7 @@ def _declare_hip(lib: C.CDLL) -> None:
         "lsk_hip_knn_rows": ([C.POINTER(KnnArgs), vp], i32),
         "lsk_hip_knn_grid": ([C.POINTER(KnnArgs), C.POINTER(GridView), vp], i32),
         "lsk_hip_knn_grid2": ([C.POINTER(KnnArgs), C.POINTER(GridView), C.POINTER(GridView), vp], i32),
+        "lsk_hip_locate_groups": ([vp, i64, vp, i64, vp, vp], i32),
         "lsk_hip_grid_decide": ([vp, vp, i64, i32, C.c_float, i32, vp, vp], i32),
         "lsk_hip_boundary_groups": ([vp, i32, i64, vp, vp, vp, C.c_int, C.c_int, vp, vp], i32),
         "lsk_hip_grid_build": ([vp, vp, i64, vp, i32, vp, vp], i32),

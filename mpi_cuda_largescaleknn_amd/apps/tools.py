@@ -4,6 +4,7 @@
     python -m mpi_cuda_largescaleknn_amd.apps.tools split in.float3 -p P -o prefix [--spatial]
            -> prefix_%06d.float3 + prefix.list (contiguous blocks, or spatial x-slabs)
     python -m mpi_cuda_largescaleknn_amd.apps.tools check in.float3 dist.float -k K [-r R] [--samples S]
+           [--queries q.float3]  (dist.float then holds hipKNN_query's output for q.float3)
            -> exact CPU oracle on sampled points, bitwise compare (replaces the reference's
               disabled '#if 0' RES dump, unorderedDataVariant.cu:215-227)
     python -m mpi_cuda_largescaleknn_amd.apps.tools cat prefix P out.float  (concatenate per-rank outputs)
@@ -65,13 +66,16 @@ def split(a) -> int:
 def check(a) -> int:
     pts = io.read_points(a.inp)
     dist = io.read_floats(a.dist_file)
-    n = pts.shape[0]
+    # --queries: the distances belong to the rows of that file (hipKNN_query), checked by
+    # brute force over all points
+    qry = io.read_points(a.queries) if a.queries else pts
+    n = qry.shape[0]
     if dist.shape[0] != n:
-        print(f"size mismatch: {dist.shape[0]} distances for {n} points")
+        print(f"size mismatch: {dist.shape[0]} distances for {n} {'queries' if a.queries else 'points'}")
         return 1
     g = torch.Generator().manual_seed(0)
     idx = torch.randint(0, n, (min(a.samples, n),), generator=g) if a.samples < n else torch.arange(n)
-    ref = K.finalize_distances(K.kth_cpu(pts, pts[idx], a.k, cut2_of(a.r), "kdtree"))
+    ref = K.finalize_distances(K.kth_cpu(pts, qry[idx], a.k, cut2_of(a.r), "brute" if a.queries else "kdtree"))
     got = dist[idx]
     bad = int((got != ref).sum())
     print(f"checked {idx.numel()} sampled points: {bad} mismatches")
@@ -125,6 +129,7 @@ def main(argv=None) -> int:
     p.add_argument("-k", type=int, required=True)
     p.add_argument("-r", type=float, default=math.inf)
     p.add_argument("--samples", type=int, default=10000)
+    p.add_argument("--queries", default=None, help="float3 file whose rows the distances belong to (hipKNN_query)")
     p = sub.add_parser("cat")
     p.add_argument("prefix")
     p.add_argument("p", type=int)

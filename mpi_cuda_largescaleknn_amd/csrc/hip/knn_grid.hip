@@ -1125,6 +1125,8 @@ __device__ bool grid_pass_impl(Lane &s, GridCtx &G, uint32_t n) {
   return true;
 }
 
+// NG: 1 = one grid whose points are the queries, 2 = two grids (below), 3 = one grid and
+// foreign queries (lsk_knn_args.foreign: as 1 without the copy test among neighbouring queries).
 // One pass over every candidate source: the index's own grid, then (NG = 2: the halo
 // re-query of a distributed run) the grid of the received halo points, whose
 // cells are walked the same way from the same wave box and (shrinking) radius; the
@@ -1133,7 +1135,7 @@ template <int MODE, int NG>
 __device__ __forceinline__ bool grid_pass_n(Lane &s, GridCtx &G, const lsk_knn_args &A, const lsk_grid_view &V,
                                             const lsk_grid_view &V1) {
   bool ok = grid_pass<MODE>(s, G, (uint32_t)A.tree[0].n);
-  if (NG > 1) {
+  if (NG == 2) {
     load_grid(G, V1, A.tree[1].pts);
     ok = ok && grid_pass<MODE>(s, G, (uint32_t)A.tree[1].n);
     load_grid(G, V, A.tree[0].pts);
@@ -1154,7 +1156,7 @@ __device__ __forceinline__ bool grid_pass_n(Lane &s, GridCtx &G, const lsk_knn_a
 #define LSK_GRID_STRIDE_MINW LSK_GRID_MINW
 #endif
 template <bool STRIDE, int NG>
-__global__ __launch_bounds__(kThreads, NG > 1 ? LSK_GRID2_MINW : (STRIDE ? LSK_GRID_STRIDE_MINW : LSK_GRID_MINW)) void knn_grid_kernel(const lsk_knn_args A, const lsk_grid_view V,
+__global__ __launch_bounds__(kThreads, NG == 2 ? LSK_GRID2_MINW : (STRIDE ? LSK_GRID_STRIDE_MINW : LSK_GRID_MINW)) void knn_grid_kernel(const lsk_knn_args A, const lsk_grid_view V,
                                                                           const lsk_grid_view V1) {
   __shared__ uint32_t lds[kWPB][kPool + 8 * kCullGroups];
   const int wid = threadIdx.x >> 6;
@@ -1357,6 +1359,10 @@ static int knn_grid_launch(const lsk_knn_args *args, const lsk_grid_view *grid, 
     return 1;
   }
   const int ng = grid1 ? 2 : 1;
+  if (A.foreign && (ng != 1 || A.groups)) {
+    lsk::set_last_error("knn_grid: foreign queries take one grid and no group list");
+    return 1;
+  }
   if (A.nq >= ((int64_t)1 << 32) || A.ntrees != ng || (ng == 1 && A.init_d2) || A.tree[0].n >= ((int64_t)1 << 32) ||
       (ng == 2 && A.tree[1].n >= ((int64_t)1 << 32)) || !grid || grid->level < 0 || grid->level > 8 ||
       (grid1 && (grid1->level < 0 || grid1->level > 8))) {
@@ -1377,6 +1383,11 @@ static int knn_grid_launch(const lsk_knn_args *args, const lsk_grid_view *grid, 
       knn_grid_kernel<true, 2><<<sblk, kThreads, 0, st>>>(A, *grid, *grid1);
     else
       knn_grid_kernel<false, 2><<<nblk, kThreads, 0, st>>>(A, *grid, *grid1);
+  } else if (A.foreign) {  // queries that are not the tree's points (lsk_knn_args.foreign)
+    if (A.pad2 >= 1)
+      knn_grid_kernel<true, 3><<<sblk, kThreads, 0, st>>>(A, *grid, *grid);
+    else
+      knn_grid_kernel<false, 3><<<nblk, kThreads, 0, st>>>(A, *grid, *grid);
   } else if (A.pad2 >= 1) {  // persistent strided form (see knn_grid_kernel); 2: a short list
     knn_grid_kernel<true, 1><<<sblk, kThreads, 0, st>>>(A, *grid, *grid);
   } else {

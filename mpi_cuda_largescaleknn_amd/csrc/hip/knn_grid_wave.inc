@@ -1,7 +1,9 @@
 // Body of one knn_grid wave (group `wave` of the launch, or A.groups[wave]); included by
 // knn_grid.hip twice: as the whole of knn_grid_kernel<false> and inside the strided loop
 // of knn_grid_kernel<true>, so the normal kernel's code is unchanged by the persistent form.
-// In scope: A, V, lds, wid, lane, wave.
+// In scope: A, V, lds, wid, lane, wave (and the template's NG).
+// NG == 3 (one grid; the queries are not the tree's points): the walk starts from the wave's box by
+// arithmetic either way; only the copy test among neighbouring queries is off.
   const uint64_t ngroups = A.groups ? (uint64_t)A.ngroups : (uint64_t)((A.nq + 63) / 64);
   if (wave >= ngroups || (A.wave_end > 0 && wave >= (uint64_t)A.wave_end)) return;
   if (A.groups && A.ngroups_dev && wave >= (uint64_t)*A.ngroups_dev) return;
@@ -64,15 +66,15 @@
   // start — 1e8, k=100: 0.086 -> 0.082 s, overflow restarts 6826 -> 344 lanes,
   // profiles/r4_s1/kernel). Exact copies are curve neighbours: compare with lanes -1 / +1
   // (the edge lanes look outside the group below).
-  bool dup;
+  bool dup = false;
   float r_est2 = -1.f;
-  {
+  if (NG != 3) {
     const float px = __shfl_up(s.qx, 1), py = __shfl_up(s.qy, 1), pz = __shfl_up(s.qz, 1);
     const float nx = __shfl_down(s.qx, 1), ny = __shfl_down(s.qy, 1), nz = __shfl_down(s.qz, 1);
     dup = (lane > 0 && px == s.qx && py == s.qy && pz == s.qz) ||
           (lane + 1 < (int)nvalid && nx == s.qx && ny == s.qy && nz == s.qz);
   }
-  if (valid && !dup) {
+  if (NG != 3 && valid && !dup) {
     const int64_t nb = lane == 0 ? qi - 1 : (lane == (int)nvalid - 1 ? qi + 1 : -1);
     if (nb >= 0 && nb < A.nq)
       dup = A.qpts[3 * nb] == s.qx && A.qpts[3 * nb + 1] == s.qy && A.qpts[3 * nb + 2] == s.qz;
@@ -94,7 +96,7 @@
   s.nudf = 0;
 
   uint32_t hist_passes = 0, limit = 0;
-  if (!valid || A.tree[0].n + (NG > 1 ? A.tree[1].n : 0) < (int64_t)k) {
+  if (!valid || A.tree[0].n + (NG == 2 ? A.tree[1].n : 0) < (int64_t)k) {
     s.state = ST_DONE;
     s.hi_b = 0;
     s.lo_b = cut_b;
@@ -104,7 +106,7 @@
     const uint32_t est_b = fbits(r_est2);
     const uint32_t off = (uint32_t)(kBins - FR.top) << FR.shift;  // (set_range aligns the start down)
     const uint32_t lo0 = est_b > off ? est_b - off : 0u;
-    const float ub = (NG > 1 && A.init_d2) ? A.init_d2[qi] : -1.f;
+    const float ub = (NG == 2 && A.init_d2) ? A.init_d2[qi] : -1.f;
     if (ub >= 0.f && ub < inf) {
       // a known upper bound (the halo re-query passes the local k-th): the range ends just
       // above it, so it cannot overflow; its start is aligned up so that kBins bins reach it

@@ -455,7 +455,7 @@ __device__ __forceinline__ lsk_tree_view pick_tree(const lsk_knn_args &A, uint32
 // compiler can count outstanding loads and the prefetch is not serialised by vmcnt(0).
 // 32-bit index math (trees hold < 2^31 points, checked on the host).
 // NT = number of trees the kernel instance handles (1: no per-lane tree selects; 3: one
-// tree in a rotated frame).
+// tree in a rotated frame; 4: one tree, foreign queries — as 1 from here on).
 template <int NT>
 __device__ __forceinline__ uint32_t load_quarter(const WaveCtx &W, uint32_t e, float &px, float &py,
                                                  float &pz) {
@@ -1062,6 +1062,36 @@ __device__ __forceinline__ float own_group_estimate(const Lane &s, uint32_t nval
   return dm * cbrtf(((float)k / (float)m0) * ((float)k / (float)m0));
 }
 
+// The same estimate for a query that is not among the tree's points (NT == 4): its M
+// nearest among the up to 64 points of one bucket (lane j of `b` holds point j), scaled to k
+// as above — the first range then follows the data's density where the query lies, not the
+// queries' own.
+__device__ __forceinline__ float bucket_estimate(const Lane &s, const Lane &b, uint32_t nvalid, uint32_t k) {
+  constexpr int M = LSK_EST_M;
+  float best[M];
+#pragma unroll
+  for (int i = 0; i < M; i++) best[i] = __builtin_inff();
+  for (uint32_t j0 = 0; j0 < nvalid; j0 += 8) {
+#pragma unroll
+    for (int t = 0; t < 8; t++) {
+      const uint32_t j = j0 + (uint32_t)t;
+      float v = lsk::dist2(s.qx - bcast64(b.qx, j), s.qy - bcast64(b.qy, j), s.qz - bcast64(b.qz, j));
+      v = (j < nvalid) ? v : __builtin_inff();
+#pragma unroll
+      for (int i = 0; i < M; i++) {
+        const float lo = fminf(best[i], v);
+        v = fmaxf(best[i], v);
+        best[i] = lo;
+      }
+    }
+  }
+  const uint32_t m0 = k < (uint32_t)M ? k : (uint32_t)M;
+  float dm = best[0];
+#pragma unroll
+  for (int i = 1; i < M; i++) dm = (i + 1 == (int)m0) ? best[i] : dm;
+  return dm * cbrtf(((float)k / (float)m0) * ((float)k / (float)m0));
+}
+
 enum : uint32_t {
   QS_OVERFLOW = 1, QS_UNDERFLOW = 2, QS_REFINE = 4, QS_LIST_INVALID = 8, QS_COLLECTED = 16,
   QS_DONE_BAND1 = 32, QS_DONE_CUT = 64, QS_DONE_ZERO = 128, QS_LIMIT = 256, QS_MISMATCH = 512,
@@ -1137,6 +1167,11 @@ extern "C" int lsk_hip_knn_rows(const lsk_knn_args *args, void *stream) {
                         "(qrot) with one tree");
     return 1;
   }
+  if (A.foreign && (A.ntrees != 1 || A.qrot || !A.qbucket || A.groups || A.foreign > 2 || A.foreign < 0)) {
+    lsk::set_last_error("knn_rows: foreign queries need one unrotated tree, their located buckets (qbucket) "
+                        "and no group list");
+    return 1;
+  }
   for (int t = 0; t < A.ntrees; t++) {
     if (A.tree[t].n >= ((int64_t)1 << 31) || A.tree[t].depth > 26 || !A.tree[t].qnodes) {
       lsk::set_last_error("knn_rows: tree too large or quarter boxes missing");
@@ -1157,12 +1192,16 @@ extern "C" int lsk_hip_knn_rows(const lsk_knn_args *args, void *stream) {
     const unsigned sblk = nblk < cap ? nblk : cap;
     if (A.ntrees > 1)
       knn_rows_kernel<LSK_RCAP, 2, true><<<sblk, kThreads, 0, st>>>(A);
+    else if (A.foreign)
+      knn_rows_kernel<LSK_RCAP, 4, true><<<sblk, kThreads, 0, st>>>(A);
     else if (A.qrot)
       knn_rows_kernel<LSK_RCAP, 3, true><<<sblk, kThreads, 0, st>>>(A);
     else
       knn_rows_kernel<LSK_RCAP, 1, true><<<sblk, kThreads, 0, st>>>(A);
   } else if (A.ntrees > 1) {
     knn_rows_kernel<LSK_RCAP, 2, false><<<nblk, kThreads, 0, st>>>(A);
+  } else if (A.foreign) {
+    knn_rows_kernel<LSK_RCAP, 4, false><<<nblk, kThreads, 0, st>>>(A);
   } else if (A.qrot) {
     knn_rows_kernel<LSK_RCAP, 3, false><<<nblk, kThreads, 0, st>>>(A);
   } else {

@@ -2,6 +2,9 @@
 // knn_rows.hip twice: as the whole of knn_rows_kernel<..., false> and inside the strided
 // loop of knn_rows_kernel<..., true>, so the normal kernel's code is unchanged by the
 // persistent form. In scope: A, lds, wid, lane, wave (and the template's RCAP, NT).
+// NT == 4 (foreign queries: not tree 0's points): the walk's own bucket is the one located
+// in the data (A.qbucket), the first range comes from that bucket's points, and nothing is
+// inferred from neighbouring queries.
   const uint64_t ngroups = A.groups ? (uint64_t)A.ngroups : (uint64_t)((A.nq + 63) / 64);
   if (wave >= ngroups || (A.wave_end > 0 && wave >= (uint64_t)A.wave_end)) return;
   if (A.groups && A.ngroups_dev && wave >= (uint64_t)*A.ngroups_dev) return;
@@ -22,7 +25,7 @@
   W.trash = lds_addr(W.L->pool) + ((uint32_t)lane & 31u) * 4u + (uint32_t)kBins * 128u;
   asm volatile("" : "+v"(W.trash));
   W.k = k;
-  W.g = g;
+  W.g = NT == 4 ? lsk::uniform(A.qbucket[g]) : g;
   W.seed = A.seed;
   W.len0 = W.len1 = W.len2 = W.len3 = W.rlen = 0;
   W.hd0 = W.hd1 = W.hd2 = W.hd3 = W.rhead = 0;
@@ -72,9 +75,33 @@
   W.wlx = lx; W.wly = ly; W.wlz = lz;
   W.whx = hx; W.why = hy; W.whz = hz;
 
-  bool dup;
-  float r_est2 = own_group_estimate(s, nvalid, k, dup);
-  if (k > (uint32_t)LSK_EST_M) {
+  bool dup = false;
+  float r_est2;
+  Lane bk;  // NT == 4: the located bucket's points, one per lane (qx.. only)
+  bool bvalid = false;
+  uint32_t bnvalid = 0;
+  if (NT == 4) {
+    const uint32_t nb0 = (W.n0 + (uint32_t)lsk::kBucket - 1u) / (uint32_t)lsk::kBucket;
+    W.g = min(W.g, nb0 > 0u ? nb0 - 1u : 0u);
+    const uint32_t b0 = W.g * (uint32_t)lsk::kBucket;
+    bnvalid = W.n0 > b0 ? min(W.n0 - b0, (uint32_t)lsk::kBucket) : 0u;
+    bvalid = (uint32_t)lane < bnvalid;
+    bk.qx = bvalid ? W.p0[3u * (b0 + (uint32_t)lane)] : 0.f;
+    bk.qy = bvalid ? W.p0[3u * (b0 + (uint32_t)lane) + 1u] : 0.f;
+    bk.qz = bvalid ? W.p0[3u * (b0 + (uint32_t)lane) + 2u] : 0.f;
+    // (A.foreign == 2: the density hint alone, the A/B of this estimate)
+    r_est2 = A.foreign == 1 ? bucket_estimate(s, bk, bnvalid, k) : -1.f;
+  } else {
+    r_est2 = own_group_estimate(s, nvalid, k, dup);
+  }
+  if (NT == 4) {
+    if (k > (uint32_t)LSK_EST_M && r_est2 > 0.f) {  // (as below, from the bucket's points)
+      const uint32_t dim = group_dimension(bk, bvalid, bnvalid);
+      const float q = (float)k / (float)LSK_EST_M;
+      if (dim == 2u) r_est2 *= cbrtf(q);
+      else if (dim == 1u) r_est2 *= q * cbrtf(q);
+    }
+  } else if (k > (uint32_t)LSK_EST_M) {
     // The estimate scales the M-th neighbour's d² by (k/M)^(2/3): 3-D data. On a plane the
     // k-th lies (k/M)^(1/3) further out in d² (2.3x at k = 100: an extra pass for almost
     // every wave of planar data before, profiles/r5_nonuniform), on a line (k/M)^(4/3).
@@ -92,8 +119,10 @@
   // pass: round 5 probed on any single copy, and line data, where float-quantised
   // coordinates give most points a copy, took 3.0 passes per wave (2e7, k = 100: 571 ->
   // 711 Mpts/s; duplicates 2005, unchanged).
+  // Foreign queries: only the data's own zeros count (the m0 nearest points of the bucket
+  // are copies of the query); a run of equal queries says nothing about the data.
   bool zero_est = valid && r_est2 == 0.f;
-  {
+  if (NT != 4) {
     const int last = (int)nvalid - 1;
     auto same = [&](int64_t i) {
       return i >= 0 && i < A.nq && qsrc[3 * i] == s.qx && qsrc[3 * i + 1] == s.qy && qsrc[3 * i + 2] == s.qz;

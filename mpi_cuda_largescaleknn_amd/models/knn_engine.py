@@ -115,6 +115,8 @@ class LocalIndex:
     grid: GridIndex | None = None
     qrot: torch.Tensor | None = None  # [n + PAD, 3]: the sorted points in the rotated frame the
                                       # keys, tree boxes and box tests use (flat_frame), or None
+    bkeys: torch.Tensor | None = None  # int32 [ceil(n / 64)]: curve key of sorted point 64 b
+                                       # (bucket_keys: built by the first foreign query)
 
     @property
     def device(self) -> torch.device:
@@ -828,3 +830,96 @@ def knn_distances(points: torch.Tensor, k: int, max_radius: float = math.inf,
     hint2 = radius_hint(index.box, index.n, k)
     out = torch.empty(index.n, dtype=torch.float32, device=points.device)
     return query(index, cfg, hint2, stats=stats, final_out=out)
+
+
+def bucket_keys(index: LocalIndex) -> torch.Tensor:
+    """Curve key (in index.box) of the first point of every bucket of `index`, cached on it.
+    Non-decreasing: the points are sorted by these keys, and refine_heavy_cells only
+    reorders points that share a key."""
+    if index.bkeys is None:
+        heads = index.pts[:index.n][::K.BUCKET].contiguous()
+        index.bkeys = K.morton(heads, index.box, with_iota=False)[0]
+    return index.bkeys
+
+
+def prepare_queries(index: LocalIndex, queries: torch.Tensor) -> tuple:
+    """Foreign queries brought into `index`'s curve order: (qsorted [nq + PAD, 3], qperm int32
+    [nq]: sorted position -> query row, qbucket int32 [ceil(nq / 64)]: the data bucket each
+    group of 64 sorted queries lies in). Keys are taken in the index's cube; queries outside
+    it (NaN included) clamp to its faces."""
+    nq = queries.shape[0]
+    keys = K.morton(queries, index.box, with_iota=False)[0]
+    skeys, qperm = K.sort_keys_iota(keys, 30)
+    qsorted = K.gather3(queries, qperm, pad=K.PAD_POINTS)
+    return qsorted, qperm, K.locate_groups(skeys, nq, bucket_keys(index))
+
+
+def query_points(index: LocalIndex, queries: torch.Tensor, cfg: KnnConfig, stats: KnnStats | None = None,
+                 out: torch.Tensor | None = None, qstatus: torch.Tensor | None = None) -> torch.Tensor:
+    """Distance from every row of `queries` (float32 [nq, 3] on the index's device) to its
+    k-th nearest point of `index` (build_index(points, grid=True)), in query order. Only the
+    index's points are candidates: a query that coincides with one finds it at distance 0,
+    and no query is a candidate for another. The cutoff and k > n behave as in `query`.
+    An index built in a rotated frame serves its own points only. `qstatus` (int32 [nq],
+    debugging): the kernels' per-query status words, in curve-sorted query order."""
+    if queries.dim() != 2 or queries.shape[1] != 3 or queries.dtype != torch.float32:
+        raise ValueError("query_points: queries must be a float32 [nq, 3] tensor")
+    if queries.device != index.device:
+        raise ValueError(f"query_points: queries on {queries.device}, the index on {index.device}")
+    if index.qrot is not None:
+        raise ValueError("query_points: an index built in a rotated frame serves its own points only")
+    queries = queries.contiguous()
+    nq, n = queries.shape[0], index.n
+    if out is None:
+        out = torch.empty(nq, dtype=torch.float32, device=index.device)
+    if nq == 0:
+        return out
+    if not K.is_gpu(index.pts):
+        out.copy_(K.finalize_distances(K.kth_cpu(index.pts[:n], queries, cfg.k, cfg.cut2)))
+        KERNELS_USED.add("cpu")
+        return out
+    if n == 0:  # no candidate at all: every answer is the cutoff
+        out.copy_(K.finalize_distances(torch.full((nq,), cfg.cut2, dtype=torch.float32, device=index.device)))
+        return out
+    qsorted, qperm, qbucket = prepare_queries(index, queries)
+    hint2 = radius_hint(index.box, n, cfg.k)
+    raw = torch.zeros(32, dtype=torch.int64, device=index.device) if stats is not None else None
+    trees = [index.tree()]
+    kw = dict(seed=SEED_BUCKETS, out_perm=qperm, out_final=out, qbucket=qbucket)
+    impl = KNN_IMPL
+    use_grid = impl == "rows" and index.grid is not None and cfg.k <= K.ROWS_MAX_K
+    if use_grid and index.grid.gate is not None:  # (the index's gate decides, as for its own points)
+        GATES_SEEN.append(index.grid.gate)
+        del GATES_SEEN[:-1024]
+    else:
+        KERNELS_USED.add("grid" if use_grid else impl)
+    fw = K.knn_gpu(qsorted, nq, trees, cfg.k, cfg.cut2, hint2, None, stats=raw, qstatus=qstatus,
+                   impl="grid" if use_grid else impl, debug_fail_mod=DEBUG_FAIL_MOD,
+                   grid=index.grid.view() if use_grid else None, expect_grid=GRID_EXPECT[0], **kw)
+    if fw.count is not None:
+        # as query()'s check: failures beyond the list's capacity rerun every query exactly
+        nfail = fw.value()
+        if use_grid and index.grid.gate is not None:
+            GRID_EXPECT[0] = bool(fw.gate_value(index.grid.gate))
+        if nfail > fw.cap:
+            K.knn_gpu(qsorted, nq, trees, cfg.k, cfg.cut2, hint2, None, impl="exact", **kw)
+        if stats is not None:
+            stats.add_fallback(nfail)
+    if stats is not None:
+        stats.add(raw)
+    return out
+
+
+def knn_query_distances(points: torch.Tensor, queries: torch.Tensor, k: int, max_radius: float = math.inf,
+                        stats: KnnStats | None = None) -> torch.Tensor:
+    """Distance from every row of `queries` to its k-th nearest neighbour among `points`
+    (both float32 [*, 3] on one device), in query order. The index is built in the points'
+    own frame (no rotated frame, no line keys), so queries off a planar set's plane work."""
+    if points.device != queries.device:
+        raise ValueError(f"knn_query_distances: points on {points.device}, queries on {queries.device}")
+    cfg = KnnConfig(k=k, max_radius=max_radius)
+    if points.shape[0] == 0:  # nothing to index: every answer is the cutoff
+        cut = torch.full((queries.shape[0],), cfg.cut2, dtype=torch.float32, device=queries.device)
+        return K.finalize_distances(cut)
+    index = build_index(points, grid=True)
+    return query_points(index, queries, cfg, stats=stats)

@@ -301,6 +301,31 @@ def fail_capacity(work: int) -> int:
     return max(1, min(work, max(1 << 26, work >> 4)))
 
 
+# Foreign queries (knn_gpu qbucket): the rows kernel places its first range from the located
+# bucket's points (True) or from the density hint alone (False: the A/B of that estimate).
+FOREIGN_ESTIMATE = True
+
+
+def locate_groups(sorted_qkeys: torch.Tensor, nq: int, bucket_keys: torch.Tensor) -> torch.Tensor:
+    """int32 [ceil(nq / 64)]: for every group of 64 curve-sorted queries, the last bucket of
+    an index whose first key (bucket_keys, non-decreasing) is <= the group's median key."""
+    ng = (nq + BUCKET - 1) // BUCKET
+    nb = bucket_keys.shape[0]
+    if not is_gpu(sorted_qkeys):
+        out = torch.zeros(ng, dtype=torch.int32)
+        if ng and nb:
+            mask = (1 << 32) - 1
+            q0 = torch.arange(ng, dtype=torch.int64) * BUCKET
+            med = sorted_qkeys.to(torch.int64)[q0 + torch.clamp(nq - q0, max=BUCKET) // 2] & mask
+            pos = torch.searchsorted(bucket_keys.to(torch.int64) & mask, med, right=True) - 1
+            out.copy_(pos.clamp_(min=0))
+        return out
+    out = torch.empty(ng, dtype=torch.int32, device=sorted_qkeys.device)
+    check(_native.hip().lsk_hip_locate_groups(_ptr(sorted_qkeys), int(nq), _ptr(bucket_keys), int(nb), _ptr(out),
+                                              _stream(sorted_qkeys)), "locate_groups")
+    return out
+
+
 class FailWord:
     """Always-on failure word of one k-NN launch: count (device int32) of the queries the
     16-bit kernel handed to the exact backstop, and the list capacity. Reading it syncs."""
@@ -356,7 +381,7 @@ def knn_gpu(qpts: torch.Tensor, nq: int, trees: list, k: int, cut2: float,
             out_perm: torch.Tensor | None = None, out_final: torch.Tensor | None = None,
             debug_fail_mod: int = 0, grid=None, ngroups_dev: torch.Tensor | None = None,
             expect_grid: bool = True, short_list: bool = False, chunks: int = 1, grid2=None,
-            qrot: torch.Tensor | None = None) -> FailWord:
+            qrot: torch.Tensor | None = None, qbucket: torch.Tensor | None = None) -> FailWord:
     """k-th squared distance for sorted queries against up to two bucket trees.
 
     trees: list of (sorted_pts_padded, nodes, qnodes, n, depth). impl: "rows" (the
@@ -385,12 +410,18 @@ def knn_gpu(qpts: torch.Tensor, nq: int, trees: list, k: int, cut2: float,
     until its last workgroup is dispatched.
     grid (impl "grid"): (slots, level, box, inf4[, gate]) of knn_engine.GridIndex — the
     cell-grid candidate source of knn_grid.hip for one tree whose points are the queries
-    (same failure list and backstop as "rows"); with a device gate (int32 [1]) the grid
+    (or, with qbucket, any queries: the walk starts from the wave's box by arithmetic;
+    same failure list and backstop as "rows"); with a device gate (int32 [1]) the grid
     kernel runs iff gate == 1 and knn_rows iff gate == 0.
     grid2 (impl "grid", two trees: the halo re-query): the second tree's grid (slots, level,
     box, inf4) — knn_grid2 walks both grids; init_d2 is allowed then.
     qrot (one tree, rows / exact): the queries in the rotated frame trees[0]'s boxes were
     built in (knn_engine.flat_frame); box tests use it, distances qpts.
+    qbucket (int32 [ceil(nq / 64)], locate_groups): the queries are NOT trees[0]'s points
+    (foreign queries, knn_engine.query_points) — one unrotated tree, no group list; the rows
+    / grid kernels run their foreign forms: the walk's own bucket and the first range come
+    from the located bucket (FOREIGN_ESTIMATE), nothing from neighbouring queries. None:
+    the queries are the tree's points, as ever.
     Returns the launch's FailWord.
     """
     if (out_perm is None) != (out_final is None):
@@ -432,6 +463,13 @@ def knn_gpu(qpts: torch.Tensor, nq: int, trees: list, k: int, cut2: float,
     a.out_perm = _ptr(out_perm)
     a.out_final = _ptr(out_final)
     a.debug_fail_mod = int(debug_fail_mod)
+    if qbucket is not None:
+        if len(trees) != 1 or qrot is not None or groups is not None or grid2 is not None:
+            raise ValueError("knn_gpu: foreign queries (qbucket) take one unrotated tree and no group list")
+        if qbucket.dtype != torch.int32 or not qbucket.is_contiguous() or qbucket.shape[0] < (nq + BUCKET - 1) // BUCKET:
+            raise ValueError("knn_gpu: qbucket must be int32 [>= ceil(nq / 64)]")
+        a.qbucket = _ptr(qbucket)
+        a.foreign = 1 if FOREIGN_ESTIMATE else 2
     lib = _native.hip()
     st = _stream(qpts)
     if impl == "exact" or k > ROWS_MAX_K:

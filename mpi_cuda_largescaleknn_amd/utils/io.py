@@ -51,6 +51,15 @@ def read_portion(path: str, rank: int = 0, size: int = 1, pin_memory: bool = Fal
     return out, begin, total
 
 
+def read_range(path: str, begin: int, count: int, pin_memory: bool = False) -> torch.Tensor:
+    """Records [begin, begin + count) of a float3 file -> [count, 3] float32 tensor."""
+    out = torch.empty((count, 3), dtype=torch.float32, pin_memory=pin_memory)
+    if count:
+        rc = _native.host().lsk_io_read(path.encode(), begin * REC, count * REC, out.data_ptr(), _nthreads())
+        _err(rc, "read", path)
+    return out
+
+
 def read_points(path: str, pin_memory: bool = False) -> torch.Tensor:
     return read_portion(path, 0, 1, pin_memory)[0]
 
