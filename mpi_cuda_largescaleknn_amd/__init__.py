@@ -38,5 +38,5 @@ def _hw_queues() -> None:
 
 _hw_queues()
 
-from .models.knn_engine import (KnnConfig, build_index, knn_distances, knn_query_distances, query,  # noqa: F401
-                                query_points)
+from .models.knn_engine import (KnnConfig, build_index, knn_distances, knn_neighbors,  # noqa: F401
+                                knn_query_distances, knn_query_neighbors, query, query_neighbors, query_points)

@@ -58,7 +58,7 @@ class TreeView(C.Structure):
     ]
 
 
-HIP_ABI = 11  # lsk_hip_abi_version() of a library matching the structs below
+HIP_ABI = 12  # lsk_hip_abi_version() of a library matching the structs below
 
 
 class KnnArgs(C.Structure):
@@ -130,6 +130,8 @@ def _declare_host(lib: C.CDLL) -> None:
         f = getattr(lib, name)
         f.argtypes = [vp, i64, vp, i64, i32, C.c_float, vp, i32]
         f.restype = None
+    lib.lsk_cpu_knn_brute.argtypes = [vp, i64, vp, i64, i32, C.c_float, vp, vp, i32]
+    lib.lsk_cpu_knn_brute.restype = None
     lib.lsk_cpu_count_below.argtypes = [vp, i64, vp, vp, i32, vp, i32]
     lib.lsk_cpu_count_below.restype = None
     lib.lsk_cpu_bounds.argtypes = [vp, i64, vp, i32]
@@ -179,6 +181,8 @@ def _declare_hip(lib: C.CDLL) -> None:
         "lsk_hip_knn_grid": ([C.POINTER(KnnArgs), C.POINTER(GridView), vp], i32),
         "lsk_hip_knn_grid2": ([C.POINTER(KnnArgs), C.POINTER(GridView), C.POINTER(GridView), vp], i32),
         "lsk_hip_locate_groups": ([vp, i64, vp, i64, vp, vp], i32),
+        "lsk_hip_knn_neighbors_ws_bytes": ([i64], C.c_size_t),
+        "lsk_hip_knn_neighbors": ([C.POINTER(TreeView), vp, vp, vp, i64, i32, C.c_float, vp, vp, vp, vp, vp, vp], i32),
         "lsk_hip_grid_decide": ([vp, vp, i64, i32, C.c_float, i32, vp, vp], i32),
         "lsk_hip_boundary_groups": ([vp, i32, i64, vp, vp, vp, C.c_int, C.c_int, vp, vp], i32),
         "lsk_hip_grid_build": ([vp, vp, i64, vp, i32, vp, vp], i32),

@@ -1,7 +1,7 @@
 """hipKNN_query — k-th-NN distances from query points to a point set.
 
     hipKNN_query <points.float3> <queries.float3> -o <dist.float> -k <k> [-r <maxRadius>]
-                 [--device auto|cuda|cpu] [--chunk N] [--stats f.json] [-v]
+                 [--device auto|cuda|cpu] [--chunk N] [--neighbors PREFIX] [--stats f.json] [-v]
 
 For every row of the query file, the distance to its k-th nearest point of the point file
 (only the points are candidates: a query that coincides with a point finds it at distance
@@ -10,6 +10,11 @@ points is built once; the queries go through it in chunks of --chunk rows (read,
 brought into the index's curve order, answered, written at their record offset), so a
 query file larger than device memory works. One process, one device: cross queries over
 several ranks are not supported.
+
+--neighbors PREFIX additionally writes the neighbour lists, chunk by chunk: PREFIX.ids
+(headerless int32 [nq][k], rows of the point file, -1 in unfilled slots) and PREFIX.dist
+(headerless float32 [nq][k]), each row ascending by (distance, row); k <= 1024. The -o file
+is then the lists' last column.
 """
 from __future__ import annotations
 
@@ -22,6 +27,7 @@ import time
 import torch
 
 from ..models import knn_engine as E
+from ..ops import kernels as K
 from ..parallel import launch as L
 from ..utils import io
 
@@ -35,6 +41,8 @@ def parse(argv: list[str]) -> argparse.Namespace:
     ap.add_argument("-r", dest="max_radius", type=float, default=math.inf)
     ap.add_argument("--device", choices=["auto", "cuda", "cpu"], default="auto")
     ap.add_argument("--chunk", type=int, default=1 << 26, help="queries per pass (default 2^26)")
+    ap.add_argument("--neighbors", default="", metavar="PREFIX",
+                    help="also write PREFIX.ids (int32 [nq][k]) and PREFIX.dist (float32 [nq][k])")
     ap.add_argument("--stats", default="", help="write run statistics to this JSON file")
     ap.add_argument("-v", dest="verbose", action="store_true")
     a = ap.parse_args(argv)
@@ -42,6 +50,8 @@ def parse(argv: list[str]) -> argparse.Namespace:
         ap.error("-k must be at least 1")
     if a.chunk < 1:
         ap.error("--chunk must be at least 1")
+    if a.neighbors and a.k > K.NEIGHBORS_MAX_K:
+        ap.error(f"--neighbors lists at most {K.NEIGHBORS_MAX_K} neighbours per query (without it, -k is unlimited)")
     return a
 
 
@@ -71,9 +81,19 @@ def main(argv: list[str] | None = None) -> int:
     t1 = time.perf_counter()
     nq = io.portion(a.queries, 0, 1)[2]
     io.write_floats(a.out, torch.empty(0, dtype=torch.float32), 0, truncate=True, total_records=nq)
+    if a.neighbors:
+        io.write_rows(a.neighbors + ".ids", torch.empty((0, a.k), dtype=torch.int32), 0, truncate=True, total_rows=nq)
+        io.write_rows(a.neighbors + ".dist", torch.empty((0, a.k), dtype=torch.float32), 0, truncate=True,
+                      total_rows=nq)
     for begin in range(0, nq, a.chunk):
         q = io.read_range(a.queries, begin, min(a.chunk, nq - begin), pin_memory=gpu).to(dev)
-        io.write_floats(a.out, E.query_points(index, q, cfg, stats=stats), begin, truncate=False)
+        if a.neighbors:
+            idx, dist = E.query_neighbors(index, q, cfg, stats=stats)
+            io.write_rows(a.neighbors + ".ids", idx, begin, truncate=False)
+            io.write_rows(a.neighbors + ".dist", dist, begin, truncate=False)
+            io.write_floats(a.out, dist[:, a.k - 1], begin, truncate=False)
+        else:
+            io.write_floats(a.out, E.query_points(index, q, cfg, stats=stats), begin, truncate=False)
     sync()
     t2 = time.perf_counter()
     if a.verbose:

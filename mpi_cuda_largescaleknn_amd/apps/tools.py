@@ -5,6 +5,7 @@
            -> prefix_%06d.float3 + prefix.list (contiguous blocks, or spatial x-slabs)
     python -m mpi_cuda_largescaleknn_amd.apps.tools check in.float3 dist.float -k K [-r R] [--samples S]
            [--queries q.float3]  (dist.float then holds hipKNN_query's output for q.float3)
+           [--neighbors PREFIX]  (also PREFIX.ids / PREFIX.dist of hipKNN_query --neighbors)
            -> exact CPU oracle on sampled points, bitwise compare (replaces the reference's
               disabled '#if 0' RES dump, unorderedDataVariant.cu:215-227)
     python -m mpi_cuda_largescaleknn_amd.apps.tools cat prefix P out.float  (concatenate per-rank outputs)
@@ -81,7 +82,29 @@ def check(a) -> int:
     print(f"checked {idx.numel()} sampled points: {bad} mismatches")
     for i in (got != ref).nonzero().flatten()[:10].tolist():
         print(f"RES {int(idx[i]):012d} = {got[i].item()!r} (oracle {ref[i].item()!r})")
+    if a.neighbors:
+        bad += _check_neighbors(a, pts, qry, idx)
     return 0 if bad == 0 else 1
+
+
+def _check_neighbors(a, pts, qry, idx) -> int:
+    """The sampled rows of PREFIX.ids / PREFIX.dist against the brute-force lists, bitwise."""
+    ids = io.read_rows(a.neighbors + ".ids", a.k, torch.int32)
+    nd = io.read_rows(a.neighbors + ".dist", a.k, torch.float32)
+    n = qry.shape[0]
+    if ids.shape[0] != n or nd.shape[0] != n:
+        print(f"size mismatch: {ids.shape[0]} id rows, {nd.shape[0]} distance rows for {n} queries")
+        return 1
+    ref_i, ref_d2 = K.knn_cpu(pts, qry[idx], a.k, cut2_of(a.r))
+    ref_d = K.finalize_distances(ref_d2.view(-1)).view(-1, a.k)
+    wrong = ((ids[idx] != ref_i) | (nd[idx] != ref_d)).any(dim=1)
+    bad = int(wrong.sum())
+    print(f"checked {idx.numel()} sampled neighbour lists: {bad} mismatches")
+    for i in wrong.nonzero().flatten()[:10].tolist():
+        j = int(((ids[idx][i] != ref_i[i]) | (nd[idx][i] != ref_d[i])).nonzero()[0])
+        print(f"ROW {int(idx[i]):012d} slot {j}: id {int(ids[idx][i][j])} dist {nd[idx][i][j].item()!r} "
+              f"(oracle id {int(ref_i[i][j])} dist {ref_d[i][j].item()!r})")
+    return bad
 
 
 def cat(a) -> int:
@@ -130,6 +153,8 @@ def main(argv=None) -> int:
     p.add_argument("-r", type=float, default=math.inf)
     p.add_argument("--samples", type=int, default=10000)
     p.add_argument("--queries", default=None, help="float3 file whose rows the distances belong to (hipKNN_query)")
+    p.add_argument("--neighbors", default=None, metavar="PREFIX",
+                   help="also check PREFIX.ids / PREFIX.dist (hipKNN_query --neighbors)")
     p = sub.add_parser("cat")
     p.add_argument("prefix")
     p.add_argument("p", type=int)

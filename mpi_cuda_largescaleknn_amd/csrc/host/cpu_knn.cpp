@@ -173,6 +173,29 @@ extern "C" void lsk_cpu_kth_brute(const float *pts, int64_t n, const float *qry,
   });
 }
 
+extern "C" void lsk_cpu_knn_brute(const float *pts, int64_t n, const float *qry, int64_t nq,
+                                  int k, float cut2, int32_t *out_idx, float *out_d2, int nthreads) {
+  const vec3f *P = (const vec3f *)pts;
+  const vec3f *Q = (const vec3f *)qry;
+  parallel_for(nq, nthreads, [&](int64_t b, int64_t e) {
+    std::vector<uint64_t> d;  // d2 bits << 32 | input row (non-negative floats order like their bits)
+    d.reserve((size_t)n);
+    for (int64_t qi = b; qi < e; qi++) {
+      d.clear();
+      for (int64_t i = 0; i < n; i++) {
+        const float v = lsk::dist2(Q[qi], P[i]);
+        if (v < cut2) d.push_back(((uint64_t)lsk::fbits(v) << 32) | (uint32_t)i);
+      }
+      const size_t m = std::min<size_t>(d.size(), (size_t)k);
+      std::partial_sort(d.begin(), d.begin() + m, d.end());
+      for (size_t j = 0; j < (size_t)k; j++) {
+        out_idx[qi * k + (int64_t)j] = j < m ? (int32_t)(uint32_t)d[j] : -1;
+        out_d2[qi * k + (int64_t)j] = j < m ? lsk::bitsf((uint32_t)(d[j] >> 32)) : cut2;
+      }
+    }
+  });
+}
+
 extern "C" void lsk_cpu_count_below(const float *pts, int64_t n, const float *qry,
                                     const float *thr, int nq, unsigned long long *counts,
                                     int nthreads) {

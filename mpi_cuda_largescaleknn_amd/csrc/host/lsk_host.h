@@ -76,6 +76,11 @@ float lsk_box_distance(const float *a, const float *b);
 // distance. cut2 = r*r (float) or +inf.
 void lsk_cpu_kth_brute(const float *pts, int64_t n, const float *qry, int64_t nq, int k,
                        float cut2, float *out_d2, int nthreads);
+// Neighbour lists by brute force: per query the first k of { (dist2, i) : dist2 < cut2 } in
+// ascending (dist2 bits, input row i) order -> out_idx / out_d2 [nq][k]; unfilled slots get
+// -1 / cut2. out_d2[q][k-1] is what lsk_cpu_kth_brute returns.
+void lsk_cpu_knn_brute(const float *pts, int64_t n, const float *qry, int64_t nq, int k,
+                       float cut2, int32_t *out_idx, float *out_d2, int nthreads);
 // Verification counts (= lsk_hip_count_below): counts[2j] += #{p : dist2(q_j,p) < thr[2j]},
 // counts[2j+1] += #{p : dist2(q_j,p) < thr[2j+1]}.
 void lsk_cpu_count_below(const float *pts, int64_t n, const float *qry, const float *thr, int nq,

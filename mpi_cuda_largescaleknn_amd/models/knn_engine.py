@@ -20,6 +20,7 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
+from .._native import NativeError
 from ..ops import kernels as K
 
 
@@ -881,9 +882,22 @@ def query_points(index: LocalIndex, queries: torch.Tensor, cfg: KnnConfig, stats
     if n == 0:  # no candidate at all: every answer is the cutoff
         out.copy_(K.finalize_distances(torch.full((nq,), cfg.cut2, dtype=torch.float32, device=index.device)))
         return out
+    _foreign_kth(index, queries, cfg, stats, out, qstatus)
+    return out
+
+
+def _foreign_kth(index: LocalIndex, queries: torch.Tensor, cfg: KnnConfig, stats: KnnStats | None,
+                 out: torch.Tensor, qstatus: torch.Tensor | None = None, want_d2: bool = False) -> tuple:
+    """The foreign-query k-th pass shared by query_points and query_neighbors (a GPU index
+    with n >= 1, nq >= 1 contiguous queries): gate, failure list and backstop as in query();
+    `out` [nq] receives the final distances in query order. Returns (qsorted, qperm, d2):
+    the curve-sorted queries, sorted position -> query row, and (want_d2) the k-th squared
+    distances in sorted order, else None."""
+    nq, n = queries.shape[0], index.n
     qsorted, qperm, qbucket = prepare_queries(index, queries)
     hint2 = radius_hint(index.box, n, cfg.k)
     raw = torch.zeros(32, dtype=torch.int64, device=index.device) if stats is not None else None
+    d2 = torch.empty(nq, dtype=torch.float32, device=index.device) if want_d2 else None
     trees = [index.tree()]
     kw = dict(seed=SEED_BUCKETS, out_perm=qperm, out_final=out, qbucket=qbucket)
     impl = KNN_IMPL
@@ -893,7 +907,7 @@ def query_points(index: LocalIndex, queries: torch.Tensor, cfg: KnnConfig, stats
         del GATES_SEEN[:-1024]
     else:
         KERNELS_USED.add("grid" if use_grid else impl)
-    fw = K.knn_gpu(qsorted, nq, trees, cfg.k, cfg.cut2, hint2, None, stats=raw, qstatus=qstatus,
+    fw = K.knn_gpu(qsorted, nq, trees, cfg.k, cfg.cut2, hint2, d2, stats=raw, qstatus=qstatus,
                    impl="grid" if use_grid else impl, debug_fail_mod=DEBUG_FAIL_MOD,
                    grid=index.grid.view() if use_grid else None, expect_grid=GRID_EXPECT[0], **kw)
     if fw.count is not None:
@@ -902,12 +916,12 @@ def query_points(index: LocalIndex, queries: torch.Tensor, cfg: KnnConfig, stats
         if use_grid and index.grid.gate is not None:
             GRID_EXPECT[0] = bool(fw.gate_value(index.grid.gate))
         if nfail > fw.cap:
-            K.knn_gpu(qsorted, nq, trees, cfg.k, cfg.cut2, hint2, None, impl="exact", **kw)
+            K.knn_gpu(qsorted, nq, trees, cfg.k, cfg.cut2, hint2, d2, impl="exact", **kw)
         if stats is not None:
             stats.add_fallback(nfail)
     if stats is not None:
         stats.add(raw)
-    return out
+    return qsorted, qperm, d2
 
 
 def knn_query_distances(points: torch.Tensor, queries: torch.Tensor, k: int, max_radius: float = math.inf,
@@ -923,3 +937,91 @@ def knn_query_distances(points: torch.Tensor, queries: torch.Tensor, k: int, max
         return K.finalize_distances(cut)
     index = build_index(points, grid=True)
     return query_points(index, queries, cfg, stats=stats)
+
+
+def query_neighbors(index: LocalIndex, queries: torch.Tensor, cfg: KnnConfig, stats: KnnStats | None = None,
+                    out_idx: torch.Tensor | None = None, out_dist: torch.Tensor | None = None) -> tuple:
+    """Neighbour lists: (idx int32 [nq, k], dist float32 [nq, k]) in query order — for every
+    row of `queries` the ids (rows of the indexed array) and distances of its k nearest
+    points of `index` within the cutoff, ascending by (distance, row): ties at any distance,
+    the k-th included, go to the lowest rows, whatever the index's internal order. Unfilled
+    slots (fewer than k points qualify) hold -1 and the value the k-th-distance API returns
+    there; dist[:, k - 1] is query_points' output bit for bit. Same inputs and limits as
+    query_points, and k <= K.NEIGHBORS_MAX_K."""
+    if queries.dim() != 2 or queries.shape[1] != 3 or queries.dtype != torch.float32:
+        raise ValueError("query_neighbors: queries must be a float32 [nq, 3] tensor")
+    if queries.device != index.device:
+        raise ValueError(f"query_neighbors: queries on {queries.device}, the index on {index.device}")
+    if index.qrot is not None:
+        raise ValueError("query_neighbors: an index built in a rotated frame serves its own points only")
+    k = cfg.k
+    if k < 1:
+        raise ValueError("query_neighbors: k must be at least 1")
+    if k > K.NEIGHBORS_MAX_K:
+        raise ValueError(f"query_neighbors: k = {k} exceeds {K.NEIGHBORS_MAX_K} neighbours per query; "
+                         "query_points / knn_query_distances give the k-th distance for any k")
+    queries = queries.contiguous()
+    nq, n = queries.shape[0], index.n
+    if out_idx is None:
+        out_idx = torch.empty((nq, k), dtype=torch.int32, device=index.device)
+    if out_dist is None:
+        out_dist = torch.empty((nq, k), dtype=torch.float32, device=index.device)
+    for t, dt in ((out_idx, torch.int32), (out_dist, torch.float32)):
+        if t.shape != (nq, k) or t.dtype != dt or not t.is_contiguous() or t.device != index.device:
+            raise ValueError("query_neighbors: out_idx int32 / out_dist float32, contiguous [nq, k] on the index's device")
+    if nq == 0:
+        return out_idx, out_dist
+    if not K.is_gpu(index.pts):
+        # (index.pts is in sorted order: ids are mapped back to input rows, so the lists are
+        # taken over the points in input order)
+        inv = torch.empty(n, dtype=torch.int64)
+        inv[index.perm[:n].long()] = torch.arange(n, dtype=torch.int64)
+        idx, d2 = K.knn_cpu(index.pts[:n][inv], queries, k, cfg.cut2)
+        out_idx.copy_(idx)
+        out_dist.copy_(K.finalize_distances(d2.view(-1)).view(nq, k))
+        KERNELS_USED.add("cpu")
+        return out_idx, out_dist
+    if n == 0:  # no candidate at all
+        out_idx.fill_(-1)
+        out_dist.copy_(K.finalize_distances(torch.full((nq * k,), cfg.cut2, dtype=torch.float32,
+                                                       device=index.device)).view(nq, k))
+        return out_idx, out_dist
+    kth = torch.empty(nq, dtype=torch.float32, device=index.device)
+    qsorted, qperm, d2 = _foreign_kth(index, queries, cfg, stats, kth, want_d2=True)
+    err = K.knn_neighbors_gpu(index.tree(), index.perm, qsorted, nq, d2, k, cfg.cut2, qperm, out_idx, out_dist)
+    LAST_NEIGHBOR_ERRORS[0] = int(err.item()) & 0xFFFFFFFF
+    if LAST_NEIGHBOR_ERRORS[0]:
+        raise NativeError(f"query_neighbors: {LAST_NEIGHBOR_ERRORS[0]} queries were handed a k-th distance that is "
+                          "not their k-th value (a bug in the k-th pass or the collect pass)")
+    return out_idx, out_dist
+
+
+# the device error word of the last query_neighbors collect pass (tests: always 0)
+LAST_NEIGHBOR_ERRORS = [0]
+
+
+def knn_query_neighbors(points: torch.Tensor, queries: torch.Tensor, k: int, max_radius: float = math.inf,
+                        stats: KnnStats | None = None) -> tuple:
+    """(idx int32 [nq, k], dist float32 [nq, k]): ids and distances of the k nearest rows of
+    `points` for every row of `queries` (both float32 [*, 3] on one device), see
+    query_neighbors. The index is built once, in the points' own frame."""
+    if points.device != queries.device:
+        raise ValueError(f"knn_query_neighbors: points on {points.device}, queries on {queries.device}")
+    cfg = KnnConfig(k=k, max_radius=max_radius)
+    if k > K.NEIGHBORS_MAX_K:
+        raise ValueError(f"knn_query_neighbors: k = {k} exceeds {K.NEIGHBORS_MAX_K} neighbours per query; "
+                         "knn_query_distances gives the k-th distance for any k")
+    if points.shape[0] == 0:  # nothing to index: every slot is unfilled
+        nq = queries.shape[0]
+        cut = torch.full((nq * k,), cfg.cut2, dtype=torch.float32, device=queries.device)
+        return (torch.full((nq, k), -1, dtype=torch.int32, device=queries.device),
+                K.finalize_distances(cut).view(nq, k))
+    index = build_index(points, grid=True)
+    return query_neighbors(index, queries, cfg, stats=stats)
+
+
+def knn_neighbors(points: torch.Tensor, k: int, max_radius: float = math.inf,
+                  stats: KnnStats | None = None) -> tuple:
+    """knn_query_neighbors with the points as their own queries: every point's list starts
+    with a point at distance 0 (itself, or the lowest row among its exact copies)."""
+    return knn_query_neighbors(points, points, k, max_radius, stats=stats)

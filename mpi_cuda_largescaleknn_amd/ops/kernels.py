@@ -602,6 +602,53 @@ def kth_cpu(points: torch.Tensor, queries: torch.Tensor, k: int, cut2: float, me
     return out
 
 
+def knn_cpu(points: torch.Tensor, queries: torch.Tensor, k: int, cut2: float) -> tuple[torch.Tensor, torch.Tensor]:
+    """CPU oracle of the neighbour lists (brute force): (idx int32 [nq, k], d2 float32 [nq, k]),
+    per query the first k of {(dist2, row) : dist2 < cut2} in ascending (dist2, row) order;
+    unfilled slots hold -1 / cut2. d2[:, k - 1] equals kth_cpu."""
+    if k < 1:
+        raise ValueError("knn_cpu: k must be at least 1")
+    pts = points.contiguous().float().cpu()
+    q = queries.contiguous().float().cpu()
+    idx = torch.empty((q.shape[0], k), dtype=torch.int32)
+    d2 = torch.empty((q.shape[0], k), dtype=torch.float32)
+    _native.host().lsk_cpu_knn_brute(_ptr(pts), pts.shape[0], _ptr(q), q.shape[0], int(k), C.c_float(cut2),
+                                     _ptr(idx), _ptr(d2), _nthreads())
+    return idx, d2
+
+
+# --------------------------------------------------------------------------- neighbour lists
+NEIGHBORS_MAX_K = 1024  # knn_neighbors.hip: a row's sort stays within 8 KB of LDS
+
+
+def knn_neighbors_gpu(tree: tuple, perm: torch.Tensor, qsorted: torch.Tensor, nq: int, kth_d2: torch.Tensor,
+                      k: int, cut2: float, out_perm: torch.Tensor, out_idx: torch.Tensor,
+                      out_dist: torch.Tensor) -> torch.Tensor:
+    """The collect pass of the neighbour lists (knn_neighbors.hip) on the current stream:
+    fills out_idx (int32 [nq, k]) / out_dist (float32 [nq, k]) in query order from the
+    curve-sorted queries' exact k-th squared distances `kth_d2`. tree: (sorted_pts_padded,
+    nodes, qnodes, n, depth), unrotated, n >= 1. Returns the pass's device error word (int32
+    [1]; non-zero: kth_d2 was not the k-th value of some query, the caller raises)."""
+    if not 1 <= k <= NEIGHBORS_MAX_K:
+        raise ValueError(f"knn_neighbors_gpu: k must be in [1, {NEIGHBORS_MAX_K}]")
+    pts, nodes, qnodes, n, depth = tree
+    for t, dt, cnt in ((perm, torch.int32, n), (out_perm, torch.int32, nq), (kth_d2, torch.float32, nq),
+                       (out_idx, torch.int32, nq * k), (out_dist, torch.float32, nq * k)):
+        if t.dtype != dt or not t.is_contiguous() or t.numel() < cnt or t.device != pts.device:
+            raise ValueError("knn_neighbors_gpu: perm / out_perm int32, kth_d2 / out_dist float32, out_idx int32, "
+                             "contiguous, on the tree's device and large enough")
+    if out_idx.numel() != nq * k or out_dist.numel() != nq * k or qsorted.shape[0] < nq:
+        raise ValueError("knn_neighbors_gpu: outputs must be [nq, k], qsorted [>= nq, 3]")
+    lib = _native.hip()
+    err = torch.zeros(1, dtype=torch.int32, device=pts.device)
+    ws = torch.empty(int(lib.lsk_hip_knn_neighbors_ws_bytes(int(nq))) // 4, dtype=torch.int32, device=pts.device)
+    tv = TreeView(_ptr(pts), _ptr(nodes), _ptr(qnodes), n, depth, 0)
+    check(lib.lsk_hip_knn_neighbors(C.byref(tv), _ptr(perm), _ptr(qsorted), _ptr(kth_d2), int(nq), int(k),
+                                    C.c_float(cut2), _ptr(out_perm), _ptr(out_idx), _ptr(out_dist), _ptr(err),
+                                    _ptr(ws), _stream(pts)), "knn_neighbors")
+    return err
+
+
 # --------------------------------------------------------------------------- halo
 UB_MAX_W = 8  # tree.hip kUbMaxW: beyond it the box-pair bound
 

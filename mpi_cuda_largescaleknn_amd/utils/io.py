@@ -93,6 +93,33 @@ def read_floats(path: str) -> torch.Tensor:
     return out
 
 
+def write_rows(path: str, data: torch.Tensor, offset_rows: int = 0, truncate: bool = True,
+               total_rows: int | None = None) -> None:
+    """pwrite the rows of a float32 or int32 [m, k] tensor at row offset (headerless, 4 k B
+    per row): the neighbour-list files of hipKNN_query --neighbors."""
+    data = data.detach().contiguous()
+    if data.device.type != "cpu":
+        data = data.cpu()
+    assert data.dim() == 2 and data.dtype in (torch.float32, torch.int32)
+    row = data.shape[1] * 4
+    flags = (1 if truncate else 0) | (2 if total_rows is not None else 0)
+    total = -1 if total_rows is None else total_rows * row
+    rc = _native.host().lsk_io_write(path.encode(), offset_rows * row, data.data_ptr(), data.numel() * 4, flags,
+                                     total, _nthreads())
+    _err(rc, "write", path)
+
+
+def read_rows(path: str, k: int, dtype: torch.dtype) -> torch.Tensor:
+    """A headerless file of float32 or int32 [*, k] rows (write_rows)."""
+    assert dtype in (torch.float32, torch.int32) and k >= 1
+    n = os.path.getsize(path) // (4 * k)
+    out = torch.empty((n, k), dtype=dtype)
+    if n:
+        rc = _native.host().lsk_io_read(path.encode(), 0, n * k * 4, out.data_ptr(), _nthreads())
+        _err(rc, "read", path)
+    return out
+
+
 def read_file_list(path: str) -> list[str]:
     """Reference readListOfFileNames, fixed: an unterminated last line is
     kept, CR is stripped, blank lines are skipped."""

@@ -6,7 +6,8 @@ code-object metadata (no GPU needed):
 
 One line per kernel: VGPRs, SGPRs, scratch bytes per lane, LDS bytes. Two libraries are
 compared by diffing the two outputs (a change that must leave existing kernels alone:
-their lines stay identical).
+their lines stay identical). Every kernel of the library is listed, e.g. `--match nb_` for the
+neighbour-list kernels of knn_neighbors.hip (nb_collect_kernel, nb_ties_kernel, nb_sort_kernel).
 """
 from __future__ import annotations
 
