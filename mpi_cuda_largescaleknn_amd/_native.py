@@ -132,6 +132,10 @@ def _declare_host(lib: C.CDLL) -> None:
         f.restype = None
     lib.lsk_cpu_knn_brute.argtypes = [vp, i64, vp, i64, i32, C.c_float, vp, vp, i32]
     lib.lsk_cpu_knn_brute.restype = None
+    lib.lsk_cpu_radius_count.argtypes = [vp, i64, vp, i64, C.c_float, vp, i32]
+    lib.lsk_cpu_radius_count.restype = None
+    lib.lsk_cpu_radius_fill.argtypes = [vp, i64, vp, i64, C.c_float, vp, vp, vp, i32]
+    lib.lsk_cpu_radius_fill.restype = None
     lib.lsk_cpu_count_below.argtypes = [vp, i64, vp, vp, i32, vp, i32]
     lib.lsk_cpu_count_below.restype = None
     lib.lsk_cpu_bounds.argtypes = [vp, i64, vp, i32]
@@ -183,6 +187,10 @@ def _declare_hip(lib: C.CDLL) -> None:
         "lsk_hip_locate_groups": ([vp, i64, vp, i64, vp, vp], i32),
         "lsk_hip_knn_neighbors_ws_bytes": ([i64], C.c_size_t),
         "lsk_hip_knn_neighbors": ([C.POINTER(TreeView), vp, vp, vp, i64, i32, C.c_float, vp, vp, vp, vp, vp, vp], i32),
+        "lsk_hip_radius_count": ([C.POINTER(TreeView), vp, i64, C.c_float, vp, vp, vp, vp], i32),
+        "lsk_hip_radius_fill": ([C.POINTER(TreeView), vp, vp, i64, C.c_float, vp, vp, vp, vp, vp, vp], i32),
+        "lsk_hip_radius_sort": ([vp, i64, i64, i64, vp, vp, i32, vp], i32),
+        "lsk_hip_radius_lds_row": ([], i32),
         "lsk_hip_grid_decide": ([vp, vp, i64, i32, C.c_float, i32, vp, vp], i32),
         "lsk_hip_boundary_groups": ([vp, i32, i64, vp, vp, vp, C.c_int, C.c_int, vp, vp], i32),
         "lsk_hip_grid_build": ([vp, vp, i64, vp, i32, vp, vp], i32),

@@ -1,0 +1,133 @@
+"""hipKNN_radius — fixed-radius search: every point within a distance of each query.
+
+    hipKNN_radius <points.float3> <queries.float3> -r <radius> -o <PREFIX> [--counts-only] [--unsorted]
+                  [--chunk N] [--max-pairs M] [--device auto|cuda|cpu] [--stats f.json] [-v]
+
+For every row of the query file, the points of the point file with dist2 < radius² (float32
+product, strict: the comparison of the -r cutoff of the k-NN tools), however many there
+are. PREFIX.count holds one int32 per query. Unless --counts-only is given the lists follow
+in CSR form: PREFIX.offsets (int64 [nq + 1], row q = [offsets[q], offsets[q + 1])),
+PREFIX.ids (int32 [total], rows of the point file) and PREFIX.dist (float32 [total]); each
+row ascending by (distance, row) unless --unsorted. All files are headerless.
+
+The index over the points is built once; the queries go through it in chunks of --chunk
+rows. A chunk with more than --max-pairs pairs is split along its counts' prefix sums into
+runs of queries that fit, so device memory bounds --max-pairs, not the output. One process,
+one device.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import math
+import sys
+import time
+
+import torch
+
+from ..models import knn_engine as E
+from ..parallel import launch as L
+from ..utils import io
+from .query import _device
+
+
+def parse(argv: list[str]) -> argparse.Namespace:
+    ap = argparse.ArgumentParser(prog="hipKNN_radius")
+    ap.add_argument("points", help="float3 file: the point set")
+    ap.add_argument("queries", help="float3 file: the query positions")
+    ap.add_argument("-r", dest="radius", type=float, required=True)
+    ap.add_argument("-o", dest="out", required=True, metavar="PREFIX",
+                    help="writes PREFIX.count and, unless --counts-only, PREFIX.offsets / .ids / .dist")
+    ap.add_argument("--counts-only", action="store_true")
+    ap.add_argument("--unsorted", action="store_true", help="rows in no particular order (cheaper)")
+    ap.add_argument("--chunk", type=int, default=1 << 24, help="queries per pass (default 2^24)")
+    ap.add_argument("--max-pairs", type=int, default=1 << 28, help="pairs held on the device at once (default 2^28)")
+    ap.add_argument("--device", choices=["auto", "cuda", "cpu"], default="auto")
+    ap.add_argument("--stats", default="", help="write run statistics to this JSON file")
+    ap.add_argument("-v", dest="verbose", action="store_true")
+    a = ap.parse_args(argv)
+    if math.isnan(a.radius) or a.radius < 0:
+        ap.error("-r must be >= 0")
+    if a.chunk < 1:
+        ap.error("--chunk must be at least 1")
+    if a.max_pairs < 1:
+        ap.error("--max-pairs must be at least 1")
+    return a
+
+
+def split_runs(counts: torch.Tensor, max_pairs: int) -> list[tuple[int, int]]:
+    """Maximal runs [s, e) of consecutive queries whose counts (CPU tensor) sum to at most
+    max_pairs. Raises ValueError(position) for a single query above max_pairs."""
+    csum = torch.cumsum(counts.long(), 0)
+    runs, s, base, m = [], 0, 0, counts.shape[0]
+    while s < m:
+        # the last e with csum[e - 1] - base <= max_pairs
+        e = int(torch.searchsorted(csum, torch.tensor(base + max_pairs), right=True))
+        if e <= s:
+            raise ValueError(s)
+        runs.append((s, e))
+        s, base = e, int(csum[e - 1])
+    return runs
+
+
+def main(argv: list[str] | None = None) -> int:
+    a = parse(list(sys.argv[1:] if argv is None else argv))
+    if L.rank_info("auto")[1] > 1:
+        sys.stderr.write("hipKNN_radius: runs as one process on one device (radius queries over several ranks "
+                         "are not supported)\n")
+        return 1
+    dev = _device(a.device)
+    gpu = dev.type == "cuda"
+    stats = E.KnnStats() if a.stats else None
+    sync = (lambda: torch.cuda.synchronize(dev)) if gpu else (lambda: None)
+    t0 = time.perf_counter()
+    points = io.read_points(a.points, pin_memory=gpu).to(dev)
+    index = E.build_index(points)
+    sync()
+    t1 = time.perf_counter()
+    nq = io.portion(a.queries, 0, 1)[2]
+    lists = not a.counts_only
+    io.write_array(a.out + ".count", torch.empty(0, dtype=torch.int32), 0, truncate=True, total=nq)
+    if lists:
+        io.write_array(a.out + ".offsets", torch.empty(0, dtype=torch.int64), 0, truncate=True, total=nq + 1)
+        io.write_array(a.out + ".ids", torch.empty(0, dtype=torch.int32), 0, truncate=True)
+        io.write_array(a.out + ".dist", torch.empty(0, dtype=torch.float32), 0, truncate=True)
+    pairs = 0  # pairs written so far = the global offset of the next row
+    for begin in range(0, nq, a.chunk):
+        q = io.read_range(a.queries, begin, min(a.chunk, nq - begin), pin_memory=gpu).to(dev)
+        counts = E.radius_counts(index, q, a.radius, stats=stats).cpu()
+        io.write_array(a.out + ".count", counts, begin, truncate=False)
+        if not lists:
+            pairs += int(counts.sum())
+            continue
+        try:
+            runs = split_runs(counts, a.max_pairs)
+        except ValueError as e:
+            s = int(e.args[0])
+            sys.stderr.write(f"hipKNN_radius: query {begin + s} alone has {int(counts[s])} points within the radius, "
+                             f"more than --max-pairs {a.max_pairs}\n")
+            return 1
+        for s, e in runs:
+            offsets, idx, dist = E.radius_neighbors(index, q[s:e], a.radius, sort=not a.unsorted,
+                                                    max_pairs=a.max_pairs)
+            io.write_array(a.out + ".offsets", offsets[:-1].cpu() + pairs, begin + s, truncate=False)
+            io.write_array(a.out + ".ids", idx, pairs, truncate=False)
+            io.write_array(a.out + ".dist", dist, pairs, truncate=False)
+            pairs += idx.shape[0]
+    if lists:
+        io.write_array(a.out + ".offsets", torch.tensor([pairs], dtype=torch.int64), nq, truncate=False)
+    sync()
+    t2 = time.perf_counter()
+    if a.verbose:
+        print(f"index of {index.n} points: {t1 - t0:.3f}s; {nq} queries, {pairs} pairs: {t2 - t1:.3f}s  "
+              f"{nq / max(t2 - t1, 1e-9) / 1e6:.1f} Mqueries/s  kernels {E.kernels_used()}", flush=True)
+    if a.stats:
+        with open(a.stats, "w") as f:
+            json.dump({"n": index.n, "nq": nq, "radius": a.radius, "pairs": pairs, "chunk": a.chunk,
+                       "max_pairs": a.max_pairs, "device": str(dev), "index_s": t1 - t0, "query_s": t2 - t1,
+                       "kernels": E.kernels_used(), "radius_search": stats.counters}, f, indent=1)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

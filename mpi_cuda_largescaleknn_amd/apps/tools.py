@@ -8,6 +8,10 @@
            [--neighbors PREFIX]  (also PREFIX.ids / PREFIX.dist of hipKNN_query --neighbors)
            -> exact CPU oracle on sampled points, bitwise compare (replaces the reference's
               disabled '#if 0' RES dump, unorderedDataVariant.cu:215-227)
+    python -m mpi_cuda_largescaleknn_amd.apps.tools rcheck in.float3 q.float3 -r R PREFIX [--samples S]
+           [--counts-only] [--unsorted]
+           -> hipKNN_radius' PREFIX.count (and .offsets / .ids / .dist) for q.float3 against the
+              brute-force oracle: every count's consistency with the offsets, sampled rows bitwise
     python -m mpi_cuda_largescaleknn_amd.apps.tools cat prefix P out.float  (concatenate per-rank outputs)
     python -m mpi_cuda_largescaleknn_amd.apps.tools cmp a.float b.float
 """
@@ -107,6 +111,57 @@ def _check_neighbors(a, pts, qry, idx) -> int:
     return bad
 
 
+def rcheck(a) -> int:
+    pts = io.read_points(a.inp)
+    qry = io.read_points(a.queries)
+    nq = qry.shape[0]
+    cut2 = cut2_of(a.r)
+    counts = io.read_array(a.prefix + ".count", torch.int32)
+    if counts.shape[0] != nq:
+        print(f"size mismatch: {counts.shape[0]} counts for {nq} queries")
+        return 1
+    g = torch.Generator().manual_seed(0)
+    idx = torch.randint(0, nq, (min(a.samples, nq),), generator=g) if a.samples < nq else torch.arange(nq)
+    ref_c = K.radius_count_cpu(pts, qry[idx], cut2)
+    wrong = counts[idx] != ref_c
+    bad = int(wrong.sum())
+    print(f"checked {idx.numel()} sampled counts: {bad} mismatches")
+    for i in wrong.nonzero().flatten()[:10].tolist():
+        print(f"COUNT {int(idx[i]):012d} = {int(counts[idx[i]])} (oracle {int(ref_c[i])})")
+    if a.counts_only:
+        return 0 if bad == 0 else 1
+    offsets = io.read_array(a.prefix + ".offsets", torch.int64)
+    ids = io.read_array(a.prefix + ".ids", torch.int32)
+    dist = io.read_array(a.prefix + ".dist", torch.float32)
+    want = torch.zeros(nq + 1, dtype=torch.int64)
+    torch.cumsum(counts, 0, dtype=torch.int64, out=want[1:])
+    if offsets.shape != want.shape or not torch.equal(offsets, want) or ids.shape[0] != int(want[nq]) \
+            or dist.shape[0] != int(want[nq]):
+        print(f"offsets are not the prefix sums of the counts, or ids ({ids.shape[0]}) / dist ({dist.shape[0]}) "
+              f"do not hold their total of {int(want[nq])} pairs")
+        return 1
+    ro, ri, rd2 = K.radius_cpu(pts, qry[idx], cut2)
+    rd = K.finalize_distances(rd2)
+    rows_bad = 0
+    for i, qi in enumerate(idx.tolist()):
+        if wrong[i]:
+            continue  # (reported above)
+        gi, gd = ids[offsets[qi]:offsets[qi + 1]], dist[offsets[qi]:offsets[qi + 1]]
+        wi, wd = ri[ro[i]:ro[i + 1]], rd[ro[i]:ro[i + 1]]
+        if a.unsorted:  # compared as sets: ids are distinct within a row
+            o, w = torch.argsort(gi.long()), torch.argsort(wi.long())
+            gi, gd, wi, wd = gi[o], gd[o], wi[w], wd[w]
+        diff = ((gi != wi) | (gd != wd)).nonzero().flatten()
+        if diff.numel():
+            rows_bad += 1
+            if rows_bad <= 10:
+                j = int(diff[0])
+                print(f"ROW {qi:012d} slot {j}: id {int(gi[j])} dist {gd[j].item()!r} "
+                      f"(oracle id {int(wi[j])} dist {wd[j].item()!r})")
+    print(f"checked {idx.numel()} sampled rows: {rows_bad} mismatches")
+    return 0 if bad + rows_bad == 0 else 1
+
+
 def cat(a) -> int:
     parts = [io.read_floats(f"{a.prefix}_{r:06d}.float") for r in range(a.p)]
     out = torch.cat(parts)
@@ -155,6 +210,14 @@ def main(argv=None) -> int:
     p.add_argument("--queries", default=None, help="float3 file whose rows the distances belong to (hipKNN_query)")
     p.add_argument("--neighbors", default=None, metavar="PREFIX",
                    help="also check PREFIX.ids / PREFIX.dist (hipKNN_query --neighbors)")
+    p = sub.add_parser("rcheck")
+    p.add_argument("inp")
+    p.add_argument("queries")
+    p.add_argument("prefix", help="the -o PREFIX of hipKNN_radius")
+    p.add_argument("-r", type=float, required=True)
+    p.add_argument("--samples", type=int, default=1000)
+    p.add_argument("--counts-only", action="store_true")
+    p.add_argument("--unsorted", action="store_true", help="rows written with --unsorted: compared as sets")
     p = sub.add_parser("cat")
     p.add_argument("prefix")
     p.add_argument("p", type=int)
@@ -164,7 +227,7 @@ def main(argv=None) -> int:
     p.add_argument("a")
     p.add_argument("b")
     a = ap.parse_args(argv)
-    return {"gen": gen, "split": split, "check": check, "cat": cat, "cmp": cmp}[a.cmd](a)
+    return {"gen": gen, "split": split, "check": check, "rcheck": rcheck, "cat": cat, "cmp": cmp}[a.cmd](a)
 
 
 if __name__ == "__main__":

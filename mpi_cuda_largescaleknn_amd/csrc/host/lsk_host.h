@@ -81,6 +81,15 @@ void lsk_cpu_kth_brute(const float *pts, int64_t n, const float *qry, int64_t nq
 // -1 / cut2. out_d2[q][k-1] is what lsk_cpu_kth_brute returns.
 void lsk_cpu_knn_brute(const float *pts, int64_t n, const float *qry, int64_t nq, int k,
                        float cut2, int32_t *out_idx, float *out_d2, int nthreads);
+// Fixed-radius search by brute force: counts[q] = #{ i : dist2(q, p_i) < cut2 } (strict; a
+// query with a NaN or infinite coordinate counts nothing), and the rows themselves in CSR
+// form: row q = [offsets[q], offsets[q+1]) (offsets: the exclusive prefix sum of the counts
+// for the same cut2, nq + 1 entries) receives every such (input row i, dist2) in ascending
+// (dist2 bits, i) order.
+void lsk_cpu_radius_count(const float *pts, int64_t n, const float *qry, int64_t nq, float cut2,
+                          int32_t *counts, int nthreads);
+void lsk_cpu_radius_fill(const float *pts, int64_t n, const float *qry, int64_t nq, float cut2,
+                         const int64_t *offsets, int32_t *out_idx, float *out_d2, int nthreads);
 // Verification counts (= lsk_hip_count_below): counts[2j] += #{p : dist2(q_j,p) < thr[2j]},
 // counts[2j+1] += #{p : dist2(q_j,p) < thr[2j+1]}.
 void lsk_cpu_count_below(const float *pts, int64_t n, const float *qry, const float *thr, int nq,

@@ -1025,3 +1025,142 @@ def knn_neighbors(points: torch.Tensor, k: int, max_radius: float = math.inf,
     """knn_query_neighbors with the points as their own queries: every point's list starts
     with a point at distance 0 (itself, or the lowest row among its exact copies)."""
     return knn_query_neighbors(points, points, k, max_radius, stats=stats)
+
+
+# ------------------------------------------------------------------ fixed-radius search
+# the device error word of the last radius_neighbors fill pass (tests: always 0)
+LAST_RADIUS_ERRORS = [0]
+
+
+def _radius_cut2(what: str, radius: float) -> float:
+    r = float(radius)
+    if math.isnan(r) or r < 0.0:
+        raise ValueError(f"{what}: radius must be >= 0 (got {radius})")
+    return cut2_of(r)
+
+
+def _radius_check(what: str, index: LocalIndex, queries: torch.Tensor) -> torch.Tensor:
+    if queries.dim() != 2 or queries.shape[1] != 3 or queries.dtype != torch.float32:
+        raise ValueError(f"{what}: queries must be a float32 [nq, 3] tensor")
+    if queries.device != index.device:
+        raise ValueError(f"{what}: queries on {queries.device}, the index on {index.device}")
+    if index.qrot is not None:
+        raise ValueError(f"{what}: an index built in a rotated frame serves its own points only")
+    return queries.contiguous()
+
+
+def _input_order(index: LocalIndex) -> torch.Tensor:
+    """The points of a CPU index in input order (index.pts is curve-sorted)."""
+    n = index.n
+    inv = torch.empty(n, dtype=torch.int64)
+    inv[index.perm[:n].long()] = torch.arange(n, dtype=torch.int64)
+    return index.pts[:n][inv]
+
+
+def _radius_sorted_queries(index: LocalIndex, queries: torch.Tensor) -> tuple:
+    """(qsorted, qperm) as prepare_queries, without locating the groups' buckets (the radius
+    walk starts at the root: it needs the curve order only)."""
+    keys = K.morton(queries, index.box, with_iota=False)[0]
+    _, qperm = K.sort_keys_iota(keys, 30)
+    return K.gather3(queries, qperm, pad=K.PAD_POINTS), qperm
+
+
+_RADIUS_STATS = ("radius_evals", "radius_nodes", "radius_buckets", "radius_box_accepts")
+
+
+def radius_counts(index: LocalIndex, queries: torch.Tensor, radius: float, stats: KnnStats | None = None,
+                  _sorted: tuple | None = None) -> torch.Tensor:
+    """int32 [nq], in query order: for every row of `queries` (float32 [nq, 3] on the index's
+    device) the number of points of `index` with dist2(q, p) < cut2_of(radius) — the strict
+    comparison of the k-th-distance cutoff, so count >= k exactly when query_points with that
+    k and max_radius = radius answers below the cutoff value. radius = 0 counts nothing,
+    radius = inf every point; a query with a NaN or infinite coordinate counts nothing. Boxes
+    that lie wholly inside a query's ball are counted without visiting their points, so large
+    radii cost far less than n distance evaluations per query. `stats` receives
+    radius_evals / radius_nodes / radius_buckets / radius_box_accepts."""
+    cut2 = _radius_cut2("radius_counts", radius)
+    queries = _radius_check("radius_counts", index, queries)
+    nq, n = queries.shape[0], index.n
+    if nq == 0 or n == 0:
+        return torch.zeros(nq, dtype=torch.int32, device=index.device)
+    if not K.is_gpu(index.pts):
+        KERNELS_USED.add("cpu")
+        return K.radius_count_cpu(index.pts[:n], queries, cut2)
+    qsorted, qperm = _sorted if _sorted is not None else _radius_sorted_queries(index, queries)
+    raw = torch.zeros(4, dtype=torch.int64, device=index.device) if stats is not None else None
+    counts = K.radius_count_gpu(index.tree(), qsorted, nq, cut2, qperm, stats=raw)
+    KERNELS_USED.add("radius")
+    if stats is not None:
+        for nm, v in zip(_RADIUS_STATS, raw.cpu().tolist()):
+            stats.counters[nm] = stats.counters.get(nm, 0) + int(v)
+    return counts
+
+
+def radius_neighbors(index: LocalIndex, queries: torch.Tensor, radius: float, sort: bool = True,
+                     max_pairs: int = 1 << 28) -> tuple:
+    """Fixed-radius neighbour lists in CSR form, in query order: (offsets int64 [nq + 1], idx
+    int32 [total], dist float32 [total]). Row q = [offsets[q], offsets[q + 1]) holds every
+    point of `index` with dist2(q, p) < cut2_of(radius) (see radius_counts), however many
+    there are: idx are rows of the indexed array, dist the final distances. sort=True: each
+    row ascending by (dist2 bits, row), the order of the neighbour lists, whatever the
+    index's internal order; sort=False: unspecified order inside a row (cheaper). More than
+    `max_pairs` pairs in all raise ValueError before anything is allocated for them."""
+    cut2 = _radius_cut2("radius_neighbors", radius)
+    queries = _radius_check("radius_neighbors", index, queries)
+    nq, n = queries.shape[0], index.n
+    dev = index.device
+    gpu = K.is_gpu(index.pts)
+    if nq == 0 or n == 0:
+        return (torch.zeros(nq + 1, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int32, device=dev),
+                torch.empty(0, dtype=torch.float32, device=dev))
+    prep = _radius_sorted_queries(index, queries) if gpu else None
+    counts = radius_counts(index, queries, radius, _sorted=prep)
+    offsets = torch.zeros(nq + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, dtype=torch.int64, out=offsets[1:])
+    total, longest = (int(v) for v in torch.stack((offsets[nq], counts.max().long())).tolist())  # the only sync
+    if total > max_pairs:
+        raise ValueError(f"radius_neighbors: {total} pairs within the radius exceed max_pairs = {max_pairs}; "
+                         "query fewer points at a time or raise max_pairs")
+    if not gpu:
+        o2, idx, d2 = K.radius_cpu(_input_order(index), queries, cut2)
+        return o2, idx, K.finalize_distances(d2)
+    qsorted, qperm = prep
+    idx, dist, err = K.radius_fill_gpu(index.tree(), index.perm, qsorted, nq, cut2, qperm, offsets, total, longest,
+                                       sort=sort)
+    LAST_RADIUS_ERRORS[0] = int(err.item()) & 0xFFFFFFFF
+    if LAST_RADIUS_ERRORS[0]:
+        raise NativeError(f"radius_neighbors: {LAST_RADIUS_ERRORS[0]} rows were not filled to their count "
+                          "(the count pass and the fill pass disagree: a bug)")
+    return offsets, idx, dist
+
+
+def radius_query_counts(points: torch.Tensor, queries: torch.Tensor, radius: float,
+                        stats: KnnStats | None = None) -> torch.Tensor:
+    """radius_counts over an index built once from `points` (both float32 [*, 3] on one
+    device), in the points' own frame."""
+    if points.device != queries.device:
+        raise ValueError(f"radius_query_counts: points on {points.device}, queries on {queries.device}")
+    if points.shape[0] == 0:  # nothing to index
+        _radius_cut2("radius_query_counts", radius)
+        return torch.zeros(queries.shape[0], dtype=torch.int32, device=queries.device)
+    return radius_counts(build_index(points), queries, radius, stats=stats)
+
+
+def radius_query_neighbors(points: torch.Tensor, queries: torch.Tensor, radius: float, sort: bool = True,
+                           max_pairs: int = 1 << 28) -> tuple:
+    """radius_neighbors over an index built once from `points`, in the points' own frame."""
+    if points.device != queries.device:
+        raise ValueError(f"radius_query_neighbors: points on {points.device}, queries on {queries.device}")
+    if points.shape[0] == 0:  # nothing to index: every row is empty
+        _radius_cut2("radius_query_neighbors", radius)
+        dev = queries.device
+        return (torch.zeros(queries.shape[0] + 1, dtype=torch.int64, device=dev),
+                torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.float32, device=dev))
+    return radius_neighbors(build_index(points), queries, radius, sort=sort, max_pairs=max_pairs)
+
+
+def radius_self_neighbors(points: torch.Tensor, radius: float, sort: bool = True, max_pairs: int = 1 << 28) -> tuple:
+    """radius_query_neighbors with the points as their own queries: for radius > 0 every
+    sorted row starts with a point at distance 0 (itself, or the lowest row among its
+    exact copies)."""
+    return radius_query_neighbors(points, points, radius, sort=sort, max_pairs=max_pairs)

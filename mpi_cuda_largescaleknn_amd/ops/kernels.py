@@ -649,6 +649,88 @@ def knn_neighbors_gpu(tree: tuple, perm: torch.Tensor, qsorted: torch.Tensor, nq
     return err
 
 
+# --------------------------------------------------------------------------- fixed-radius search
+RADIUS_LDS_ROW = 4096  # radius.hip kLdsRow: longer rows are sorted in global memory
+
+
+def radius_count_cpu(points: torch.Tensor, queries: torch.Tensor, cut2: float) -> torch.Tensor:
+    """CPU oracle (brute force): int32 [nq], per query the number of rows of `points` with
+    dist2 < cut2 (strict)."""
+    pts = points.contiguous().float().cpu()
+    q = queries.contiguous().float().cpu()
+    counts = torch.empty(q.shape[0], dtype=torch.int32)
+    _native.host().lsk_cpu_radius_count(_ptr(pts), pts.shape[0], _ptr(q), q.shape[0], C.c_float(cut2),
+                                        _ptr(counts), _nthreads())
+    return counts
+
+
+def radius_cpu(points: torch.Tensor, queries: torch.Tensor, cut2: float) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """CPU oracle of the fixed-radius lists (brute force), CSR: (offsets int64 [nq + 1], idx
+    int32 [total], d2 float32 [total]); row q holds every (row of `points`, dist2) with
+    dist2 < cut2 in ascending (dist2 bits, row) order."""
+    pts = points.contiguous().float().cpu()
+    q = queries.contiguous().float().cpu()
+    nq = q.shape[0]
+    offsets = torch.zeros(nq + 1, dtype=torch.int64)
+    torch.cumsum(radius_count_cpu(pts, q, cut2), 0, dtype=torch.int64, out=offsets[1:])
+    total = int(offsets[nq])
+    idx = torch.empty(total, dtype=torch.int32)
+    d2 = torch.empty(total, dtype=torch.float32)
+    _native.host().lsk_cpu_radius_fill(_ptr(pts), pts.shape[0], _ptr(q), nq, C.c_float(cut2), _ptr(offsets),
+                                       _ptr(idx), _ptr(d2), _nthreads())
+    return offsets, idx, d2
+
+
+def _radius_args(what: str, tree: tuple, qsorted: torch.Tensor, nq: int, cut2: float, out_perm: torch.Tensor):
+    pts, nodes, qnodes, n, depth = tree
+    if not cut2 >= 0.0:
+        raise ValueError(f"{what}: cut2 must be >= 0")
+    if qsorted.shape[0] < nq or out_perm.dtype != torch.int32 or out_perm.numel() < nq \
+            or not out_perm.is_contiguous() or out_perm.device != pts.device or qsorted.device != pts.device:
+        raise ValueError(f"{what}: qsorted [>= nq, 3] and out_perm int32 [nq], contiguous, on the tree's device")
+    return TreeView(_ptr(pts), _ptr(nodes), _ptr(qnodes), n, depth, 0)
+
+
+def radius_count_gpu(tree: tuple, qsorted: torch.Tensor, nq: int, cut2: float, out_perm: torch.Tensor,
+                     stats: torch.Tensor | None = None) -> torch.Tensor:
+    """The count pass of the fixed-radius search (radius.hip) on the current stream: int32
+    [nq] in query order, per query the number of the tree's points with dist2 < cut2. tree:
+    (sorted_pts_padded, nodes, qnodes, n, depth), unrotated, n >= 1; qsorted / out_perm: the
+    curve-sorted queries and sorted query -> query row. stats: optional zeroed int64 [4]
+    (distance evaluations, nodes popped, buckets scanned, whole-box acceptances)."""
+    tv = _radius_args("radius_count_gpu", tree, qsorted, nq, cut2, out_perm)
+    counts = torch.empty(nq, dtype=torch.int32, device=tree[0].device)
+    check(_native.hip().lsk_hip_radius_count(C.byref(tv), _ptr(qsorted), int(nq), C.c_float(cut2), _ptr(out_perm),
+                                             _ptr(counts), _ptr(stats), _stream(tree[0])), "radius_count")
+    return counts
+
+
+def radius_fill_gpu(tree: tuple, perm: torch.Tensor, qsorted: torch.Tensor, nq: int, cut2: float,
+                    out_perm: torch.Tensor, offsets: torch.Tensor, total: int, longest: int,
+                    sort: bool = True) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The fill and sort passes of the fixed-radius search on the current stream: (idx int32
+    [total], dist float32 [total], err) for the CSR rows `offsets` (int64 [nq + 1] on the
+    device, the prefix sum of radius_count_gpu's counts for the same cut2; total =
+    offsets[nq], longest >= the longest row). idx holds rows of the indexed array (through
+    perm), dist final distances; sort: rows ascending by (dist2 bits, row), else in walk
+    order. err: the device error word (int32 [1]; non-zero: count and fill disagreed, the
+    caller raises)."""
+    tv = _radius_args("radius_fill_gpu", tree, qsorted, nq, cut2, out_perm)
+    dev = tree[0].device
+    if offsets.dtype != torch.int64 or offsets.numel() != nq + 1 or not offsets.is_contiguous() or offsets.device != dev \
+            or perm.dtype != torch.int32 or perm.numel() < tree[3] or not perm.is_contiguous() or perm.device != dev:
+        raise ValueError("radius_fill_gpu: offsets int64 [nq + 1] and perm int32 [n], contiguous, on the tree's device")
+    lib = _native.hip()
+    idx = torch.empty(total, dtype=torch.int32, device=dev)
+    dist = torch.empty(total, dtype=torch.float32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    check(lib.lsk_hip_radius_fill(C.byref(tv), _ptr(perm), _ptr(qsorted), int(nq), C.c_float(cut2), _ptr(out_perm),
+                                  _ptr(offsets), _ptr(idx), _ptr(dist), _ptr(err), _stream(tree[0])), "radius_fill")
+    check(lib.lsk_hip_radius_sort(_ptr(offsets), int(nq), int(total), int(longest), _ptr(idx), _ptr(dist),
+                                  1 if sort else 0, _stream(tree[0])), "radius_sort")
+    return idx, dist, err
+
+
 # --------------------------------------------------------------------------- halo
 UB_MAX_W = 8  # tree.hip kUbMaxW: beyond it the box-pair bound
 

@@ -120,6 +120,38 @@ def read_rows(path: str, k: int, dtype: torch.dtype) -> torch.Tensor:
     return out
 
 
+_ARRAY_TYPES = (torch.float32, torch.int32, torch.int64)
+
+
+def write_array(path: str, data: torch.Tensor, offset: int = 0, truncate: bool = True,
+                total: int | None = None) -> None:
+    """pwrite a 1-D float32, int32 or int64 tensor at element offset `offset` (headerless):
+    the count / offsets / ids / dist files of hipKNN_radius."""
+    data = data.detach().contiguous()
+    if data.device.type != "cpu":
+        data = data.cpu()
+    assert data.dim() == 1 and data.dtype in _ARRAY_TYPES
+    sz = data.element_size()
+    flags = (1 if truncate else 0) | (2 if total is not None else 0)
+    rc = _native.host().lsk_io_write(path.encode(), offset * sz, data.data_ptr(), data.numel() * sz, flags,
+                                     -1 if total is None else total * sz, _nthreads())
+    _err(rc, "write", path)
+
+
+def read_array(path: str, dtype: torch.dtype, begin: int = 0, count: int | None = None) -> torch.Tensor:
+    """Elements [begin, begin + count) (default: to the end) of a headerless file of
+    float32, int32 or int64 values (write_array)."""
+    assert dtype in _ARRAY_TYPES
+    sz = torch.empty(0, dtype=dtype).element_size()
+    if count is None:
+        count = max(0, os.path.getsize(path) // sz - begin)
+    out = torch.empty(count, dtype=dtype)
+    if count:
+        rc = _native.host().lsk_io_read(path.encode(), begin * sz, count * sz, out.data_ptr(), _nthreads())
+        _err(rc, "read", path)
+    return out
+
+
 def read_file_list(path: str) -> list[str]:
     """Reference readListOfFileNames, fixed: an unterminated last line is
     kept, CR is stripped, blank lines are skipped."""

@@ -1,0 +1,102 @@
+#!/usr/bin/env python3
+"""Fixed-radius search throughput on one GPU, beside the k-nearest lists of the same size.
+
+    python scripts/radius_bench.py [--points 1e7] [--queries 1e6] [--mean 100] [--steps 5] [--warmup 2]
+
+Uniform points in the unit cube and uniform queries from another seed; the radius is the one
+whose ball holds --mean points at the data's density (queries near the faces see fewer, so
+the measured mean is a little lower; it is printed). On one index, device-synchronised host
+clock, medians over the steps after the warm-up steps, the four timed alternately step by
+step so that drift on a shared host hits them alike:
+  * counts:    radius_counts;
+  * sorted:    radius_neighbors (count + prefix sum + fill + row sort);
+  * unsorted:  radius_neighbors(sort=False);
+  * knn_lists: query_neighbors at k = --mean on the same index and queries — the yardstick:
+               lists of the same size that need a selection pass first.
+Prints one JSON line. Sampled rows are checked against brute force.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import math
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+from mpi_cuda_largescaleknn_amd.models import knn_engine as E  # noqa: E402
+from mpi_cuda_largescaleknn_amd.ops import kernels as K  # noqa: E402
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--points", type=float, default=1e7)
+    ap.add_argument("--queries", type=float, default=1e6)
+    ap.add_argument("--mean", type=int, default=100, help="mean neighbours per query, and the yardstick's k")
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.stderr.write("radius_bench: needs a GPU (a CPU timing says nothing about it)\n")
+        return 2
+    n, nq, k = int(a.points), int(a.queries), a.mean
+    dev = torch.device("cuda", 0)
+    p = torch.rand((n, 3), generator=torch.Generator(device=dev).manual_seed(1), device=dev)
+    q = torch.rand((nq, 3), generator=torch.Generator(device=dev).manual_seed(2), device=dev)
+    r = (k / (n * 4.0 / 3.0 * math.pi)) ** (1.0 / 3.0)
+    index = E.build_index(p, grid=True)
+    E.bucket_keys(index)
+    cfg = E.KnnConfig(k=k)
+    out = {}
+    cases = {
+        "counts": lambda: out.__setitem__("counts", E.radius_counts(index, q, r)),
+        "sorted": lambda: out.__setitem__("sorted", E.radius_neighbors(index, q, r)),
+        "unsorted": lambda: out.__setitem__("unsorted", E.radius_neighbors(index, q, r, sort=False)),
+        "knn_lists": lambda: out.__setitem__("knn", E.query_neighbors(index, q, cfg)),
+    }
+    times = {name: [] for name in cases}
+    for step in range(a.warmup + a.steps):
+        for name, fn in cases.items():
+            out.clear()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            if step >= a.warmup:
+                times[name].append(time.perf_counter() - t0)
+    med = {name: statistics.median(ts) for name, ts in times.items()}
+
+    offsets, idx, dist = E.radius_neighbors(index, q, r)
+    counts = E.radius_counts(index, q, r)
+    total = int(offsets[-1])
+    smp = torch.randint(0, nq, (64,), generator=torch.Generator().manual_seed(3))
+    ro, ri, rd2 = K.radius_cpu(p.cpu(), q[smp.to(dev)].cpu(), E.cut2_of(r))
+    rd = K.finalize_distances(rd2)
+    off = offsets.cpu()
+    exact = 0
+    for j, qi in enumerate(smp.tolist()):
+        gi, gd = idx[off[qi]:off[qi + 1]].cpu(), dist[off[qi]:off[qi + 1]].cpu()
+        exact += int(torch.equal(gi, ri[ro[j]:ro[j + 1]]) and torch.equal(gd, rd[ro[j]:ro[j + 1]]))
+    consistent = bool(torch.equal(torch.cumsum(counts, 0, dtype=torch.int64), offsets[1:]))
+    rec = {
+        "points": n, "queries": nq, "radius": r, "mean_count": total / nq, "max_count": int(counts.max()),
+        "pairs": total, "steps": a.steps, "warmup": a.warmup,
+        "counts_s": med["counts"], "sorted_s": med["sorted"], "unsorted_s": med["unsorted"],
+        "knn_lists_k": k, "knn_lists_s": med["knn_lists"],
+        "spread": {name: [min(ts), max(ts)] for name, ts in times.items()},
+        "sorted_over_knn_lists": med["sorted"] / med["knn_lists"],
+        "sorted_Mpairs_per_s": total / med["sorted"] / 1e6, "counts_Mqueries_per_s": nq / med["counts"] / 1e6,
+        "sampled_exact": f"{exact}/64", "offsets_are_count_sums": consistent,
+    }
+    print(json.dumps(rec), flush=True)
+    return 0 if exact == 64 and consistent else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
