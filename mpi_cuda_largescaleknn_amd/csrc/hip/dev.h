@@ -133,6 +133,13 @@ static inline unsigned lsk_blocks(int64_t n, int per_block, unsigned cap = 0) {
   return (unsigned)b;
 }
 
+// A complete view of a non-empty bucket tree: what the kernels that walk one tree from its
+// root (knn_neighbors.hip, radius.hip) require of their caller.
+static inline bool lsk_tree_ok(const lsk_tree_view *tree) {
+  return tree && tree->n >= 1 && tree->n < ((int64_t)1 << 31) && tree->depth >= 0 && tree->depth <= 30 &&
+         tree->nodes && tree->pts && lsk_hip_tree_depth(tree->n) == tree->depth;
+}
+
 // Fill nwords 32-bit words with v by a kernel instead of hipMemsetAsync: memset nodes in a
 // captured HIP graph were seen not to re-run on later replays (ROCm 7.0: the 88-byte and
 // 4-byte ones of the level census, and the grid's slot table — tests/test_gpu_graph.py read

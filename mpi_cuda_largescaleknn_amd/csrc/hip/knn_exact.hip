@@ -27,7 +27,7 @@
 //     they share a bin) into 256 32-bit LDS bins. The bin holding the k-th value becomes the next
 //     [lo, hi); a range of width 1 is the answer. <= 4 counting passes (8 bits each).
 // Same canonical dist² (common.h) as the oracle and the production kernel: bit-identical.
-#include "dev.h"
+#include "ball_walk.h"
 
 namespace {
 
@@ -48,10 +48,7 @@ constexpr int kBins = 256;
 #endif
 constexpr int kStep = LSK_EXACT_STEP;
 static_assert(kStep >= 1 && kStep <= 6, "a wave tests at most 64 boxes per expansion");
-// DFS stack entries per wave: <= ceil(30 / step) expansions of 2^step - 1 siblings + 1
-constexpr int kStack = ((30 + kStep - 1) / kStep * ((1 << kStep) - 1) + 1 + 31) / 32 * 32 < 128
-                           ? 128
-                           : ((30 + kStep - 1) / kStep * ((1 << kStep) - 1) + 1 + 31) / 32 * 32;
+constexpr int kStack = lsk::walk_stack(kStep);  // DFS stack entries per wave
 
 // W = 1: each wave owns its query (hist per wave). W > 1: the block's W waves share one
 // query and one histogram, each walking a contiguous 1/W of every tree's buckets: the

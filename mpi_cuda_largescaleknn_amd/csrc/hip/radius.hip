@@ -1,14 +1,12 @@
 // Fixed-radius search: for every query the number of points with d² < cut2, and those
 // points themselves as CSR rows (ids in input order + distances).
 //
-// No selection pass: a radius query is the ball walk of knn_neighbors.hip with the same
-// radius in every lane, run twice (count, then fill into rows sized by the counts), plus a
-// sort over rows of varying length.
+// No selection pass: a radius query is the group walk of ball_walk.h with the same radius
+// in every lane, run twice (count, then fill into rows sized by the counts), plus a sort
+// over rows of varying length.
 //
-//  1. radius_walk_kernel<false> (count): one wave owns 64 curve-consecutive sorted queries
-//     (lane = query) and walks the bucket tree once for the group (wave-uniform DFS, 64-ary
-//     expansion, stack in LDS). A box is pruned when it is not closer than cut2 to the
-//     group's box. Every popped node is tested per lane: nearer corner >= cut2: nothing of
+//  1. radius_walk_kernel<false> (count): a box is pruned when it is not closer than cut2 to
+//     the group's box. Every popped node is tested per lane: nearer corner >= cut2: nothing of
 //     it counts for the lane; farthest corner < cut2: all of it does, so the lane adds the
 //     node's population (clipped at n) without a distance evaluation and ignores the node's
 //     subtree. Per-axis float differences, squares and fma are monotone, so no point inside
@@ -20,21 +18,20 @@
 //     [offsets[row], offsets[row + 1]) and never writes past the row's end; a lane that
 //     would, or that ends short of it, bumps the error word (count and fill disagree: a bug).
 //  3. radius_sort_lds_kernel: rows of up to kLdsRow pairs, sorted in place by
-//     (d² bits << 32 | id) with a bitonic network in LDS, 32 consecutive rows per block
+//     (d² bits << 32 | id) with the LDS network of row_sort.h, 32 consecutive rows per block
 //     padded to the longest of them, then final_distance. radius_sort_big_kernel: longer
 //     rows, one block per row, the same keys by an all-ascending bitonic network over
 //     global memory (any length: the virtual padding up to the next power of two is +inf
 //     and never moves, so comparators that reach past the row's end are skipped).
-#include "dev.h"
+#include "ball_walk.h"
+#include "row_sort.h"
 
 namespace {
 
-using lsk::bitsf;
 using lsk::fbits;
+using lsk::finalised;
 
 constexpr int kWaves = 4;      // waves per block, one query group each
-constexpr int kStep = 6;       // levels per tree expansion (64 boxes, one per lane)
-constexpr int kStack = 320;    // DFS stack entries per wave: 5 expansions x 63 siblings + 1
 // Longest row the LDS sort takes: 4096 64-bit keys = 32 KB per block, so four blocks (and
 // their 16 waves) share a CU's 160 KB; twice that would halve the blocks of the common
 // short-row case for rows that are rare.
@@ -59,64 +56,23 @@ struct RadArgs {
                              // buckets scanned, whole-box acceptances
 };
 
-__device__ __forceinline__ float readlane_f(float v, int j) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), j));
-}
-
-__device__ __forceinline__ bool finite3(float x, float y, float z) {
-  const float inf = __builtin_inff();
-  return fabsf(x) < inf && fabsf(y) < inf && fabsf(z) < inf;
-}
-
-// As knn_neighbors.hip::expand: lane l < 2^step tests descendant l of `node`, the kept ones
-// (that cover at least one bucket < nb) are pushed. Returns the new stack pointer.
-template <class Keep>
-__device__ __forceinline__ uint32_t expand(const float4 *nodes, uint32_t node, int32_t lvl, int32_t depth,
-                                           int64_t nb, uint32_t *stk, uint32_t sp, int lane, Keep keep) {
-  const int32_t step = min(kStep, depth - lvl);
-  const uint32_t nc = 1u << step;
-  const uint32_t child = (node << step) + (uint32_t)lane;
-  bool need = false;
-  if ((uint32_t)lane < nc) {
-    const int32_t span_lg = depth - (lvl + step);
-    const int64_t first = ((int64_t)child - ((int64_t)1 << (lvl + step))) << span_lg;
-    if (first < nb) {
-      const float4 lo4 = nodes[2 * child], hi4 = nodes[2 * child + 1];
-      need = keep(lo4, hi4);
-    }
-  }
-  const uint64_t m = __ballot(need);
-  if (need) stk[sp + __popcll(m & ((1ull << lane) - 1ull))] = child;
-  __builtin_amdgcn_wave_barrier();
-  return sp + (uint32_t)__popcll(m);
-}
-
 template <bool kFill>
 __global__ __launch_bounds__(kWaves * 64) void radius_walk_kernel(const RadArgs A) {
-  __shared__ uint32_t stk_all[kWaves][kStack];
+  __shared__ uint32_t stk_all[kWaves][lsk::kWalkStack];
   const int wid = threadIdx.x >> 6;
   const int lane = lsk::lane_id();
-  uint32_t *stk = stk_all[wid];
   const int64_t g = (int64_t)blockIdx.x * kWaves + wid;
   if (g * lsk::kBucket >= A.nq) return;  // (wave-uniform)
-  const int64_t qi = g * lsk::kBucket + lane;
-  const bool valid = qi < A.nq;
+  const lsk::GroupQuery Q = lsk::load_group(g, lane, A.qpts, A.out_perm, A.nq);
   const float cut2 = A.cut2;
-  const float inf = __builtin_inff();
-  float qx = 0.f, qy = 0.f, qz = 0.f;
-  int64_t row = 0, cur = 0, end = 0;
-  if (valid) {
-    qx = A.qpts[3 * qi];
-    qy = A.qpts[3 * qi + 1];
-    qz = A.qpts[3 * qi + 2];
-    row = (int64_t)A.out_perm[qi];
-    if (kFill) {
-      cur = A.offsets[row];
-      end = A.offsets[row + 1];
-    }
+  const float qx = Q.x, qy = Q.y, qz = Q.z;
+  const int64_t row = Q.row;
+  int64_t cur = 0, end = 0;
+  if (kFill && Q.valid) {
+    cur = A.offsets[row];
+    end = A.offsets[row + 1];
   }
-  // a query with a non-finite coordinate has d² = inf or NaN to every point: no neighbours
-  const bool live = valid && finite3(qx, qy, qz) && cut2 > 0.f;
+  const bool live = Q.finite && cut2 > 0.f;
   uint32_t count = 0;
   bool bad = false;
   // count: the lane took a whole node when the stack stood at cov_sp; everything popped
@@ -126,92 +82,62 @@ __global__ __launch_bounds__(kWaves * 64) void radius_walk_kernel(const RadArgs 
   uint32_t s_evals = 0, s_accepts = 0, s_nodes = 0, s_buckets = 0;
 
   if (__ballot(live)) {
-    const lsk::box3f gb{{lsk::wave_min(live ? qx : inf), lsk::wave_min(live ? qy : inf), lsk::wave_min(live ? qz : inf)},
-                        {lsk::wave_max(live ? qx : -inf), lsk::wave_max(live ? qy : -inf),
-                         lsk::wave_max(live ? qz : -inf)}};
+    const lsk::box3f gb = lsk::group_box(Q, live);
     const lsk::vec3f q{qx, qy, qz};
     const lsk_tree_view &T = A.T;
-    const int32_t depth = T.depth;
-    const int64_t nb = (T.n + lsk::kBucket - 1) / lsk::kBucket;
-    const float4 *nodes = (const float4 *)T.nodes;
-    uint32_t sp = 1;
-    if (lane == 0) stk[0] = 1u;
-    __builtin_amdgcn_wave_barrier();
-    while (sp > 0) {
-      sp--;
-      const uint32_t node = lsk::uniform(stk[sp]);
-      const int32_t lvl = 31 - __clz(node);
-      const float4 lo4 = nodes[2 * node], hi4 = nodes[2 * node + 1];
-      s_nodes++;
-      bool use = live && !bad && lsk::box_dist2(q, {lo4.x, lo4.y, lo4.z}, {hi4.x, hi4.y, hi4.z}) < cut2;
-      if (!kFill) {
-        if (cov && sp < cov_sp) cov = false;
-        use = use && !cov;
-        if (use) {
-          const float fx = fmaxf(fabsf(lo4.x - qx), fabsf(hi4.x - qx));
-          const float fy = fmaxf(fabsf(lo4.y - qy), fabsf(hi4.y - qy));
-          const float fz = fmaxf(fabsf(lo4.z - qz), fabsf(hi4.z - qz));
-          if (lsk::dist2(fx, fy, fz) < cut2) {
-            // the node's points: its buckets, the last one clipped at n
-            const int32_t span_lg = depth - lvl;
-            const int64_t first = ((int64_t)node - ((int64_t)1 << lvl)) << span_lg;
-            const int64_t p0 = first * lsk::kBucket;
-            const int64_t p1 = min(T.n, (first + ((int64_t)1 << span_lg)) * lsk::kBucket);
-            if (p1 > p0) count += (uint32_t)(p1 - p0);
-            cov = true;
-            cov_sp = sp;
-            use = false;
-            s_accepts++;
-          }
-        }
-      }
-      if (!__ballot(use)) continue;
-      if (lvl < depth) {
-        sp = expand(nodes, node, lvl, depth, nb, stk, sp, lane, [&](const float4 &l4, const float4 &h4) {
-          return lsk::box_box_dist2(gb, {{l4.x, l4.y, l4.z}, {h4.x, h4.y, h4.z}}) < cut2;
-        });
-        continue;
-      }
-      // a bucket: the lanes that need it test its points one by one
-      const int64_t base = ((int64_t)node - ((int64_t)1 << depth)) * lsk::kBucket;
-      if (base >= T.n) continue;
-      const int cnt = (int)min((int64_t)lsk::kBucket, T.n - base);
-      s_buckets++;
-      const int64_t pi = base + lane;
-      float px = 0.f, py = 0.f, pz = 0.f;
-      uint32_t pid = 0;
-      if (lane < cnt) {
-        px = T.pts[3 * pi];
-        py = T.pts[3 * pi + 1];
-        pz = T.pts[3 * pi + 2];
-        if (kFill) pid = A.perm[pi];
-      }
-      if (use) s_evals += (uint32_t)cnt;
-      for (int j = 0; j < cnt; j++) {
-        const float x = readlane_f(px, j), y = readlane_f(py, j), z = readlane_f(pz, j);
-        uint32_t id = 0;
-        if (kFill) id = (uint32_t)__builtin_amdgcn_readlane((int)pid, j);
-        if (use) {
-          const float d2 = lsk::dist2(qx - x, qy - y, qz - z);
-          if (d2 < cut2) {
-            if (!kFill) {
-              count++;
-            } else if (cur < end) {
-              A.out_idx[cur] = (int32_t)id;
-              A.out_dist[cur] = fbits(d2);
-              cur++;
-            } else {  // more than the count pass saw: stop appending
-              bad = true;
-              use = false;
+    lsk::ball_walk<true>(
+        T, stk_all[wid], lane,
+        [&](const float4 &lo4, const float4 &hi4) { return lsk::box_box_dist2(gb, lsk::box_of(lo4, hi4)) < cut2; },
+        [&](uint32_t node, int32_t lvl, uint32_t sp, const float4 &lo4, const float4 &hi4) {
+          s_nodes++;
+          bool use = live && !bad && lsk::box_dist2(q, {lo4.x, lo4.y, lo4.z}, {hi4.x, hi4.y, hi4.z}) < cut2;
+          if (!kFill) {
+            if (cov && sp < cov_sp) cov = false;
+            use = use && !cov;
+            if (use) {
+              const float fx = fmaxf(fabsf(lo4.x - qx), fabsf(hi4.x - qx));
+              const float fy = fmaxf(fabsf(lo4.y - qy), fabsf(hi4.y - qy));
+              const float fz = fmaxf(fabsf(lo4.z - qz), fabsf(hi4.z - qz));
+              if (lsk::dist2(fx, fy, fz) < cut2) {
+                // the node's points: its buckets, the last one clipped at n
+                const int32_t span_lg = T.depth - lvl;
+                const int64_t first = ((int64_t)node - ((int64_t)1 << lvl)) << span_lg;
+                const int64_t p0 = first * lsk::kBucket;
+                const int64_t p1 = min(T.n, (first + ((int64_t)1 << span_lg)) * lsk::kBucket);
+                if (p1 > p0) count += (uint32_t)(p1 - p0);
+                cov = true;
+                cov_sp = sp;
+                use = false;
+                s_accepts++;
+              }
             }
           }
-        }
-      }
-    }
+          return use;
+        },
+        // a bucket: the lanes that need it test its points one by one
+        [&](uint32_t node, bool use) {
+          const bool evals = use;
+          const int cnt = lsk::scan_bucket<kFill>(T, A.perm, node, lane, Q, use, [&](float d2, uint32_t id, bool &use) {
+            if (d2 < cut2) {
+              if (!kFill) {
+                count++;
+              } else if (cur < end) {
+                A.out_idx[cur] = (int32_t)id;
+                A.out_dist[cur] = fbits(d2);
+                cur++;
+              } else {  // more than the count pass saw: stop appending
+                bad = true;
+                use = false;
+              }
+            }
+          });
+          if (cnt) s_buckets++;
+          if (evals) s_evals += (uint32_t)cnt;
+        });
   }
 
   if (!kFill) {
-    if (valid) A.counts[row] = (int32_t)count;
+    if (Q.valid) A.counts[row] = (int32_t)count;
     if (A.stats) {
       const uint32_t e = lsk::wave_sum(s_evals), a = lsk::wave_sum(s_accepts);
       if (lane == 0) {
@@ -221,13 +147,9 @@ __global__ __launch_bounds__(kWaves * 64) void radius_walk_kernel(const RadArgs 
         atomicAdd(&A.stats[3], (unsigned long long)a);
       }
     }
-  } else if (valid && (bad || cur != end)) {
+  } else if (Q.valid && (bad || cur != end)) {
     atomicAdd(A.err, 1u);
   }
-}
-
-__device__ __forceinline__ uint32_t finalised(uint32_t d2bits) {
-  return fbits(lsk::final_distance(bitsf(d2bits)));
 }
 
 // Rows [blockIdx * kSortRows, + kSortRows) that fit the LDS, kLdsRow >> lg at a time, each
@@ -261,28 +183,13 @@ __global__ __launch_bounds__(kSortThreads) void radius_sort_lds_kernel(const int
         const int64_t len = off[r + 1] - off[r];
         if (len <= (int64_t)kLdsRow && (int64_t)c < len) {
           const int64_t o = off[r] + c;
-          v = ((uint64_t)dist[o] << 32) | (uint32_t)idx[o];
+          v = lsk::pack_key(dist[o], idx[o]);
         }
       }
       key[e] = v;
     }
     __syncthreads();
-    // bitonic network over every aligned kpad segment, all ascending (padding sorts last)
-    for (uint32_t kk = 2; kk <= kpad; kk <<= 1) {
-      for (uint32_t j = kk >> 1; j > 0; j >>= 1) {
-        for (uint32_t t = threadIdx.x; t < (uint32_t)kLdsRow / 2; t += kSortThreads) {
-          const uint32_t i = ((t & ~(j - 1u)) << 1) | (t & (j - 1u));
-          const uint32_t p = i | j;
-          const bool asc = ((i & (kpad - 1u)) & kk) == 0u;
-          const uint64_t a = key[i], b = key[p];
-          if ((a > b) == asc && a != b) {
-            key[i] = b;
-            key[p] = a;
-          }
-        }
-        __syncthreads();
-      }
-    }
+    lsk::sort_rows_lds(key, kLdsRow, kpad, kSortThreads);
     for (uint32_t e = threadIdx.x; e < (uint32_t)kLdsRow; e += kSortThreads) {
       const uint32_t r = r0 + (e >> lg), c = e & (kpad - 1u);
       if (r < nrows) {
@@ -290,8 +197,8 @@ __global__ __launch_bounds__(kSortThreads) void radius_sort_lds_kernel(const int
         if (len <= (int64_t)kLdsRow && (int64_t)c < len) {
           const int64_t o = off[r] + c;
           const uint64_t v = key[e];
-          idx[o] = (int32_t)(uint32_t)v;
-          dist[o] = finalised((uint32_t)(v >> 32));
+          idx[o] = lsk::key_id(v);
+          dist[o] = finalised(lsk::key_d2bits(v));
         }
       }
     }
@@ -300,13 +207,12 @@ __global__ __launch_bounds__(kSortThreads) void radius_sort_lds_kernel(const int
 }
 
 __device__ __forceinline__ void order_pair(int32_t *idx, uint32_t *dist, int64_t i, int64_t p) {
-  const uint64_t a = ((uint64_t)dist[i] << 32) | (uint32_t)idx[i];
-  const uint64_t b = ((uint64_t)dist[p] << 32) | (uint32_t)idx[p];
+  const uint64_t a = lsk::pack_key(dist[i], idx[i]), b = lsk::pack_key(dist[p], idx[p]);
   if (a > b) {
-    idx[i] = (int32_t)(uint32_t)b;
-    dist[i] = (uint32_t)(b >> 32);
-    idx[p] = (int32_t)(uint32_t)a;
-    dist[p] = (uint32_t)(a >> 32);
+    idx[i] = lsk::key_id(b);
+    dist[i] = lsk::key_d2bits(b);
+    idx[p] = lsk::key_id(a);
+    dist[p] = lsk::key_d2bits(a);
   }
 }
 
@@ -355,11 +261,6 @@ __global__ __launch_bounds__(256) void radius_finalise_kernel(uint32_t *__restri
     dist[i] = finalised(dist[i]);
 }
 
-bool tree_ok(const lsk_tree_view *tree) {
-  return tree && tree->n >= 1 && tree->n < ((int64_t)1 << 31) && tree->depth >= 0 && tree->depth <= 30 &&
-         tree->nodes && tree->pts && lsk_hip_tree_depth(tree->n) == tree->depth;
-}
-
 }  // namespace
 
 extern "C" int lsk_hip_radius_lds_row(void) { return kLdsRow; }
@@ -367,7 +268,7 @@ extern "C" int lsk_hip_radius_lds_row(void) { return kLdsRow; }
 extern "C" int lsk_hip_radius_count(const lsk_tree_view *tree, const float *qpts, int64_t nq, float cut2,
                                     const uint32_t *out_perm, int32_t *counts, unsigned long long *stats,
                                     void *stream) {
-  if (!tree_ok(tree) || nq < 0 || nq >= ((int64_t)1 << 32) || !(cut2 >= 0.f)) {
+  if (!lsk_tree_ok(tree) || nq < 0 || nq >= ((int64_t)1 << 32) || !(cut2 >= 0.f)) {
     lsk::set_last_error("radius_count: tree view incomplete (1 <= n < 2^31, depth = tree_depth(n)), "
                         "0 <= nq < 2^32 or cut2 not >= 0");
     return 1;
@@ -394,7 +295,7 @@ extern "C" int lsk_hip_radius_count(const lsk_tree_view *tree, const float *qpts
 extern "C" int lsk_hip_radius_fill(const lsk_tree_view *tree, const uint32_t *perm, const float *qpts, int64_t nq,
                                    float cut2, const uint32_t *out_perm, const int64_t *offsets, int32_t *out_idx,
                                    float *out_dist, uint32_t *err, void *stream) {
-  if (!tree_ok(tree) || nq < 0 || nq >= ((int64_t)1 << 32) || !(cut2 >= 0.f)) {
+  if (!lsk_tree_ok(tree) || nq < 0 || nq >= ((int64_t)1 << 32) || !(cut2 >= 0.f)) {
     lsk::set_last_error("radius_fill: tree view incomplete (1 <= n < 2^31, depth = tree_depth(n)), "
                         "0 <= nq < 2^32 or cut2 not >= 0");
     return 1;

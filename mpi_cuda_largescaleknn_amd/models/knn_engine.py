@@ -843,16 +843,41 @@ def bucket_keys(index: LocalIndex) -> torch.Tensor:
     return index.bkeys
 
 
-def prepare_queries(index: LocalIndex, queries: torch.Tensor) -> tuple:
+def prepare_queries(index: LocalIndex, queries: torch.Tensor, locate: bool = True) -> tuple:
     """Foreign queries brought into `index`'s curve order: (qsorted [nq + PAD, 3], qperm int32
     [nq]: sorted position -> query row, qbucket int32 [ceil(nq / 64)]: the data bucket each
-    group of 64 sorted queries lies in). Keys are taken in the index's cube; queries outside
-    it (NaN included) clamp to its faces."""
+    group of 64 sorted queries lies in, or None without `locate`: a walk that starts at the
+    root needs the curve order only). Keys are taken in the index's cube; queries outside it
+    (NaN included) clamp to its faces."""
     nq = queries.shape[0]
     keys = K.morton(queries, index.box, with_iota=False)[0]
     skeys, qperm = K.sort_keys_iota(keys, 30)
     qsorted = K.gather3(queries, qperm, pad=K.PAD_POINTS)
-    return qsorted, qperm, K.locate_groups(skeys, nq, bucket_keys(index))
+    return qsorted, qperm, K.locate_groups(skeys, nq, bucket_keys(index)) if locate else None
+
+
+def _check_foreign(what: str, index: LocalIndex, queries: torch.Tensor) -> torch.Tensor:
+    """The foreign queries of the public function `what`, checked and contiguous."""
+    if queries.dim() != 2 or queries.shape[1] != 3 or queries.dtype != torch.float32:
+        raise ValueError(f"{what}: queries must be a float32 [nq, 3] tensor")
+    if queries.device != index.device:
+        raise ValueError(f"{what}: queries on {queries.device}, the index on {index.device}")
+    if index.qrot is not None:
+        raise ValueError(f"{what}: an index built in a rotated frame serves its own points only")
+    return queries.contiguous()
+
+
+def _input_order(index: LocalIndex) -> torch.Tensor:
+    """The points of a CPU index in input order (index.pts is curve-sorted)."""
+    n = index.n
+    inv = torch.empty(n, dtype=torch.int64)
+    inv[index.perm[:n].long()] = torch.arange(n, dtype=torch.int64)
+    return index.pts[:n][inv]
+
+
+def _cutoff_distances(shape: tuple, cut2: float, device: torch.device) -> torch.Tensor:
+    """No candidate at all: float32 `shape`, every slot the finalised cutoff."""
+    return K.finalize_distances(torch.full((math.prod(shape),), cut2, dtype=torch.float32, device=device)).view(shape)
 
 
 def query_points(index: LocalIndex, queries: torch.Tensor, cfg: KnnConfig, stats: KnnStats | None = None,
@@ -863,13 +888,7 @@ def query_points(index: LocalIndex, queries: torch.Tensor, cfg: KnnConfig, stats
     and no query is a candidate for another. The cutoff and k > n behave as in `query`.
     An index built in a rotated frame serves its own points only. `qstatus` (int32 [nq],
     debugging): the kernels' per-query status words, in curve-sorted query order."""
-    if queries.dim() != 2 or queries.shape[1] != 3 or queries.dtype != torch.float32:
-        raise ValueError("query_points: queries must be a float32 [nq, 3] tensor")
-    if queries.device != index.device:
-        raise ValueError(f"query_points: queries on {queries.device}, the index on {index.device}")
-    if index.qrot is not None:
-        raise ValueError("query_points: an index built in a rotated frame serves its own points only")
-    queries = queries.contiguous()
+    queries = _check_foreign("query_points", index, queries)
     nq, n = queries.shape[0], index.n
     if out is None:
         out = torch.empty(nq, dtype=torch.float32, device=index.device)
@@ -880,7 +899,7 @@ def query_points(index: LocalIndex, queries: torch.Tensor, cfg: KnnConfig, stats
         KERNELS_USED.add("cpu")
         return out
     if n == 0:  # no candidate at all: every answer is the cutoff
-        out.copy_(K.finalize_distances(torch.full((nq,), cfg.cut2, dtype=torch.float32, device=index.device)))
+        out.copy_(_cutoff_distances((nq,), cfg.cut2, index.device))
         return out
     _foreign_kth(index, queries, cfg, stats, out, qstatus)
     return out
@@ -933,8 +952,7 @@ def knn_query_distances(points: torch.Tensor, queries: torch.Tensor, k: int, max
         raise ValueError(f"knn_query_distances: points on {points.device}, queries on {queries.device}")
     cfg = KnnConfig(k=k, max_radius=max_radius)
     if points.shape[0] == 0:  # nothing to index: every answer is the cutoff
-        cut = torch.full((queries.shape[0],), cfg.cut2, dtype=torch.float32, device=queries.device)
-        return K.finalize_distances(cut)
+        return _cutoff_distances((queries.shape[0],), cfg.cut2, queries.device)
     index = build_index(points, grid=True)
     return query_points(index, queries, cfg, stats=stats)
 
@@ -948,19 +966,13 @@ def query_neighbors(index: LocalIndex, queries: torch.Tensor, cfg: KnnConfig, st
     slots (fewer than k points qualify) hold -1 and the value the k-th-distance API returns
     there; dist[:, k - 1] is query_points' output bit for bit. Same inputs and limits as
     query_points, and k <= K.NEIGHBORS_MAX_K."""
-    if queries.dim() != 2 or queries.shape[1] != 3 or queries.dtype != torch.float32:
-        raise ValueError("query_neighbors: queries must be a float32 [nq, 3] tensor")
-    if queries.device != index.device:
-        raise ValueError(f"query_neighbors: queries on {queries.device}, the index on {index.device}")
-    if index.qrot is not None:
-        raise ValueError("query_neighbors: an index built in a rotated frame serves its own points only")
+    queries = _check_foreign("query_neighbors", index, queries)
     k = cfg.k
     if k < 1:
         raise ValueError("query_neighbors: k must be at least 1")
     if k > K.NEIGHBORS_MAX_K:
         raise ValueError(f"query_neighbors: k = {k} exceeds {K.NEIGHBORS_MAX_K} neighbours per query; "
                          "query_points / knn_query_distances give the k-th distance for any k")
-    queries = queries.contiguous()
     nq, n = queries.shape[0], index.n
     if out_idx is None:
         out_idx = torch.empty((nq, k), dtype=torch.int32, device=index.device)
@@ -972,19 +984,15 @@ def query_neighbors(index: LocalIndex, queries: torch.Tensor, cfg: KnnConfig, st
     if nq == 0:
         return out_idx, out_dist
     if not K.is_gpu(index.pts):
-        # (index.pts is in sorted order: ids are mapped back to input rows, so the lists are
-        # taken over the points in input order)
-        inv = torch.empty(n, dtype=torch.int64)
-        inv[index.perm[:n].long()] = torch.arange(n, dtype=torch.int64)
-        idx, d2 = K.knn_cpu(index.pts[:n][inv], queries, k, cfg.cut2)
+        # (ids are rows of the input array: the lists are taken over the points in input order)
+        idx, d2 = K.knn_cpu(_input_order(index), queries, k, cfg.cut2)
         out_idx.copy_(idx)
         out_dist.copy_(K.finalize_distances(d2.view(-1)).view(nq, k))
         KERNELS_USED.add("cpu")
         return out_idx, out_dist
     if n == 0:  # no candidate at all
         out_idx.fill_(-1)
-        out_dist.copy_(K.finalize_distances(torch.full((nq * k,), cfg.cut2, dtype=torch.float32,
-                                                       device=index.device)).view(nq, k))
+        out_dist.copy_(_cutoff_distances((nq, k), cfg.cut2, index.device))
         return out_idx, out_dist
     kth = torch.empty(nq, dtype=torch.float32, device=index.device)
     qsorted, qperm, d2 = _foreign_kth(index, queries, cfg, stats, kth, want_d2=True)
@@ -1013,9 +1021,8 @@ def knn_query_neighbors(points: torch.Tensor, queries: torch.Tensor, k: int, max
                          "knn_query_distances gives the k-th distance for any k")
     if points.shape[0] == 0:  # nothing to index: every slot is unfilled
         nq = queries.shape[0]
-        cut = torch.full((nq * k,), cfg.cut2, dtype=torch.float32, device=queries.device)
         return (torch.full((nq, k), -1, dtype=torch.int32, device=queries.device),
-                K.finalize_distances(cut).view(nq, k))
+                _cutoff_distances((nq, k), cfg.cut2, queries.device))
     index = build_index(points, grid=True)
     return query_neighbors(index, queries, cfg, stats=stats)
 
@@ -1039,32 +1046,6 @@ def _radius_cut2(what: str, radius: float) -> float:
     return cut2_of(r)
 
 
-def _radius_check(what: str, index: LocalIndex, queries: torch.Tensor) -> torch.Tensor:
-    if queries.dim() != 2 or queries.shape[1] != 3 or queries.dtype != torch.float32:
-        raise ValueError(f"{what}: queries must be a float32 [nq, 3] tensor")
-    if queries.device != index.device:
-        raise ValueError(f"{what}: queries on {queries.device}, the index on {index.device}")
-    if index.qrot is not None:
-        raise ValueError(f"{what}: an index built in a rotated frame serves its own points only")
-    return queries.contiguous()
-
-
-def _input_order(index: LocalIndex) -> torch.Tensor:
-    """The points of a CPU index in input order (index.pts is curve-sorted)."""
-    n = index.n
-    inv = torch.empty(n, dtype=torch.int64)
-    inv[index.perm[:n].long()] = torch.arange(n, dtype=torch.int64)
-    return index.pts[:n][inv]
-
-
-def _radius_sorted_queries(index: LocalIndex, queries: torch.Tensor) -> tuple:
-    """(qsorted, qperm) as prepare_queries, without locating the groups' buckets (the radius
-    walk starts at the root: it needs the curve order only)."""
-    keys = K.morton(queries, index.box, with_iota=False)[0]
-    _, qperm = K.sort_keys_iota(keys, 30)
-    return K.gather3(queries, qperm, pad=K.PAD_POINTS), qperm
-
-
 _RADIUS_STATS = ("radius_evals", "radius_nodes", "radius_buckets", "radius_box_accepts")
 
 
@@ -1079,14 +1060,14 @@ def radius_counts(index: LocalIndex, queries: torch.Tensor, radius: float, stats
     radii cost far less than n distance evaluations per query. `stats` receives
     radius_evals / radius_nodes / radius_buckets / radius_box_accepts."""
     cut2 = _radius_cut2("radius_counts", radius)
-    queries = _radius_check("radius_counts", index, queries)
+    queries = _check_foreign("radius_counts", index, queries)
     nq, n = queries.shape[0], index.n
     if nq == 0 or n == 0:
         return torch.zeros(nq, dtype=torch.int32, device=index.device)
     if not K.is_gpu(index.pts):
         KERNELS_USED.add("cpu")
         return K.radius_count_cpu(index.pts[:n], queries, cut2)
-    qsorted, qperm = _sorted if _sorted is not None else _radius_sorted_queries(index, queries)
+    qsorted, qperm = _sorted if _sorted is not None else prepare_queries(index, queries, locate=False)[:2]
     raw = torch.zeros(4, dtype=torch.int64, device=index.device) if stats is not None else None
     counts = K.radius_count_gpu(index.tree(), qsorted, nq, cut2, qperm, stats=raw)
     KERNELS_USED.add("radius")
@@ -1106,14 +1087,14 @@ def radius_neighbors(index: LocalIndex, queries: torch.Tensor, radius: float, so
     index's internal order; sort=False: unspecified order inside a row (cheaper). More than
     `max_pairs` pairs in all raise ValueError before anything is allocated for them."""
     cut2 = _radius_cut2("radius_neighbors", radius)
-    queries = _radius_check("radius_neighbors", index, queries)
+    queries = _check_foreign("radius_neighbors", index, queries)
     nq, n = queries.shape[0], index.n
     dev = index.device
     gpu = K.is_gpu(index.pts)
     if nq == 0 or n == 0:
         return (torch.zeros(nq + 1, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int32, device=dev),
                 torch.empty(0, dtype=torch.float32, device=dev))
-    prep = _radius_sorted_queries(index, queries) if gpu else None
+    prep = prepare_queries(index, queries, locate=False)[:2] if gpu else None
     counts = radius_counts(index, queries, radius, _sorted=prep)
     offsets = torch.zeros(nq + 1, dtype=torch.int64, device=dev)
     torch.cumsum(counts, 0, dtype=torch.int64, out=offsets[1:])

@@ -621,6 +621,16 @@ def knn_cpu(points: torch.Tensor, queries: torch.Tensor, k: int, cut2: float) ->
 NEIGHBORS_MAX_K = 1024  # knn_neighbors.hip: a row's sort stays within 8 KB of LDS
 
 
+def _walk_view(what: str, tree: tuple, qsorted: torch.Tensor, nq: int, out_perm: torch.Tensor) -> TreeView:
+    """The view of `tree` for a group walk (ball_walk.h) by `what`, whose curve-sorted queries
+    and sorted query -> query row map are checked."""
+    pts, nodes, qnodes, n, depth = tree
+    if qsorted.shape[0] < nq or out_perm.dtype != torch.int32 or out_perm.numel() < nq \
+            or not out_perm.is_contiguous() or out_perm.device != pts.device or qsorted.device != pts.device:
+        raise ValueError(f"{what}: qsorted [>= nq, 3] and out_perm int32 [nq], contiguous, on the tree's device")
+    return TreeView(_ptr(pts), _ptr(nodes), _ptr(qnodes), n, depth, 0)
+
+
 def knn_neighbors_gpu(tree: tuple, perm: torch.Tensor, qsorted: torch.Tensor, nq: int, kth_d2: torch.Tensor,
                       k: int, cut2: float, out_perm: torch.Tensor, out_idx: torch.Tensor,
                       out_dist: torch.Tensor) -> torch.Tensor:
@@ -631,18 +641,18 @@ def knn_neighbors_gpu(tree: tuple, perm: torch.Tensor, qsorted: torch.Tensor, nq
     [1]; non-zero: kth_d2 was not the k-th value of some query, the caller raises)."""
     if not 1 <= k <= NEIGHBORS_MAX_K:
         raise ValueError(f"knn_neighbors_gpu: k must be in [1, {NEIGHBORS_MAX_K}]")
-    pts, nodes, qnodes, n, depth = tree
-    for t, dt, cnt in ((perm, torch.int32, n), (out_perm, torch.int32, nq), (kth_d2, torch.float32, nq),
+    tv = _walk_view("knn_neighbors_gpu", tree, qsorted, nq, out_perm)
+    pts = tree[0]
+    for t, dt, cnt in ((perm, torch.int32, tree[3]), (kth_d2, torch.float32, nq),
                        (out_idx, torch.int32, nq * k), (out_dist, torch.float32, nq * k)):
         if t.dtype != dt or not t.is_contiguous() or t.numel() < cnt or t.device != pts.device:
-            raise ValueError("knn_neighbors_gpu: perm / out_perm int32, kth_d2 / out_dist float32, out_idx int32, "
+            raise ValueError("knn_neighbors_gpu: perm int32, kth_d2 / out_dist float32, out_idx int32, "
                              "contiguous, on the tree's device and large enough")
-    if out_idx.numel() != nq * k or out_dist.numel() != nq * k or qsorted.shape[0] < nq:
-        raise ValueError("knn_neighbors_gpu: outputs must be [nq, k], qsorted [>= nq, 3]")
+    if out_idx.numel() != nq * k or out_dist.numel() != nq * k:
+        raise ValueError("knn_neighbors_gpu: outputs must be [nq, k]")
     lib = _native.hip()
     err = torch.zeros(1, dtype=torch.int32, device=pts.device)
     ws = torch.empty(int(lib.lsk_hip_knn_neighbors_ws_bytes(int(nq))) // 4, dtype=torch.int32, device=pts.device)
-    tv = TreeView(_ptr(pts), _ptr(nodes), _ptr(qnodes), n, depth, 0)
     check(lib.lsk_hip_knn_neighbors(C.byref(tv), _ptr(perm), _ptr(qsorted), _ptr(kth_d2), int(nq), int(k),
                                     C.c_float(cut2), _ptr(out_perm), _ptr(out_idx), _ptr(out_dist), _ptr(err),
                                     _ptr(ws), _stream(pts)), "knn_neighbors")
@@ -682,13 +692,9 @@ def radius_cpu(points: torch.Tensor, queries: torch.Tensor, cut2: float) -> tupl
 
 
 def _radius_args(what: str, tree: tuple, qsorted: torch.Tensor, nq: int, cut2: float, out_perm: torch.Tensor):
-    pts, nodes, qnodes, n, depth = tree
     if not cut2 >= 0.0:
         raise ValueError(f"{what}: cut2 must be >= 0")
-    if qsorted.shape[0] < nq or out_perm.dtype != torch.int32 or out_perm.numel() < nq \
-            or not out_perm.is_contiguous() or out_perm.device != pts.device or qsorted.device != pts.device:
-        raise ValueError(f"{what}: qsorted [>= nq, 3] and out_perm int32 [nq], contiguous, on the tree's device")
-    return TreeView(_ptr(pts), _ptr(nodes), _ptr(qnodes), n, depth, 0)
+    return _walk_view(what, tree, qsorted, nq, out_perm)
 
 
 def radius_count_gpu(tree: tuple, qsorted: torch.Tensor, nq: int, cut2: float, out_perm: torch.Tensor,

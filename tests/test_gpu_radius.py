@@ -151,6 +151,36 @@ def test_both_sort_paths():
     assert same(got, ref), report(got, ref)
 
 
+def test_row_sort_of_hand_made_rows():
+    """lsk_hip_radius_sort alone on hand-made CSR rows: lengths around every padding step of
+    the LDS network and on both sides of K.RADIUS_LDS_ROW, keys with many repeats of one d²
+    under different ids. Against torch.sort of the packed (d² bits << 32 | id) keys."""
+    lens = [0, 1, 2, 3, 5, 64, 65, K.RADIUS_LDS_ROW - 1, K.RADIUS_LDS_ROW, K.RADIUS_LDS_ROW + 1]
+    g = torch.Generator().manual_seed(77)
+    bits, ids = [], []
+    for m in lens:
+        # d² bits of finite non-negative floats, about three ids per value; ids distinct within the row
+        pool = torch.randint(0, 0x7F800000, (max(1, m // 3),), generator=g, dtype=torch.int64)
+        bits.append(pool[torch.randint(0, pool.numel(), (m,), generator=g)])
+        ids.append(torch.randperm(3 * m + 1, generator=g)[:m])
+    bits, ids = torch.cat(bits), torch.cat(ids)
+    offsets = torch.zeros(len(lens) + 1, dtype=torch.int64)
+    offsets[1:] = torch.cumsum(torch.tensor(lens), 0)
+    total = int(offsets[-1])
+    d2 = bits.int().view(torch.float32)
+    assert bool(torch.isfinite(d2).all()) and bool((d2 >= 0).all())
+    packed = (bits << 32) | ids
+    want = torch.cat([torch.sort(packed[a:b]).values for a, b in zip(offsets[:-1].tolist(), offsets[1:].tolist())])
+    assert int((want[1:] >> 32 == want[:-1] >> 32).sum()) > total // 2  # repeats of one d² survive the setup
+    off_d = offsets.to(DEV)
+    for sort, ref in ((1, want), (0, packed)):
+        idx, dist = ids.int().to(DEV), d2.to(DEV)
+        _native.check(_native.hip().lsk_hip_radius_sort(K._ptr(off_d), len(lens), total, max(lens), K._ptr(idx),
+                                                       K._ptr(dist), sort, K._stream(idx)), "radius_sort")
+        assert torch.equal(idx.cpu(), (ref & 0xFFFFFFFF).int()), f"sort={sort}: ids"
+        assert torch.equal(dist.cpu(), final((ref >> 32).int().view(torch.float32))), f"sort={sort}: distances"
+
+
 def test_seventy_thousand_copies():
     """Rows far beyond the LDS limit made of one distance: 70 000 copies of one point among
     5000 others; a query on the copies lists exactly their rows first, ascending."""
