@@ -1,11 +1,15 @@
 """hipKNN_radius — fixed-radius search: every point within a distance of each query.
 
-    hipKNN_radius <points.float3> <queries.float3> -r <radius> -o <PREFIX> [--counts-only] [--unsorted]
-                  [--chunk N] [--max-pairs M] [--device auto|cuda|cpu] [--stats f.json] [-v]
+    hipKNN_radius <points.float3> <queries.float3> (-r <radius> | --radii FILE | --point-radii FILE) [--squared]
+                  -o <PREFIX> [--counts-only] [--unsorted] [--chunk N] [--max-pairs M]
+                  [--device auto|cuda|cpu] [--stats f.json] [-v]
 
 For every row of the query file, the points of the point file with dist2 < radius² (float32
 product, strict: the comparison of the -r cutoff of the k-NN tools), however many there
-are. PREFIX.count holds one int32 per query. Unless --counts-only is given the lists follow
+are. Exactly one of: -r, one radius for all; --radii, a headerless float32 file with one
+radius per query row (gather: dist2 < the query's radius²); --point-radii, one radius per
+point row (scatter: dist2 < the point's radius², the points whose own ball holds the query).
+--squared: the values are the squared cutoffs themselves. PREFIX.count holds one int32 per query. Unless --counts-only is given the lists follow
 in CSR form: PREFIX.offsets (int64 [nq + 1], row q = [offsets[q], offsets[q + 1])),
 PREFIX.ids (int32 [total], rows of the point file) and PREFIX.dist (float32 [total]); each
 row ascending by (distance, row) unless --unsorted. All files are headerless.
@@ -31,11 +35,30 @@ from ..utils import io
 from .query import _device
 
 
+def add_radius_options(ap: argparse.ArgumentParser) -> None:
+    """Exactly one of -r / --radii / --point-radii, and --squared (also lsknn_tools rcheck)."""
+    g = ap.add_mutually_exclusive_group(required=True)
+    g.add_argument("-r", dest="radius", type=float, default=None, help="one radius for every query")
+    g.add_argument("--radii", default=None, metavar="FILE",
+                   help="headerless float32 file, one radius per query row: points with dist2 < its square")
+    g.add_argument("--point-radii", default=None, metavar="FILE",
+                   help="headerless float32 file, one radius per point row: points whose own ball holds the query")
+    ap.add_argument("--squared", action="store_true", help="the given values are squared cutoffs")
+
+
+def read_radii(path: str, what: str, rows: int, of: str) -> torch.Tensor:
+    """A radius file of `rows` float32 values; ValueError names both lengths otherwise."""
+    r = io.read_array(path, torch.float32)
+    if r.shape[0] != rows:
+        raise ValueError(f"{what} {path} holds {r.shape[0]} values, {of} has {rows} rows")
+    return r
+
+
 def parse(argv: list[str]) -> argparse.Namespace:
     ap = argparse.ArgumentParser(prog="hipKNN_radius")
     ap.add_argument("points", help="float3 file: the point set")
     ap.add_argument("queries", help="float3 file: the query positions")
-    ap.add_argument("-r", dest="radius", type=float, required=True)
+    add_radius_options(ap)
     ap.add_argument("-o", dest="out", required=True, metavar="PREFIX",
                     help="writes PREFIX.count and, unless --counts-only, PREFIX.offsets / .ids / .dist")
     ap.add_argument("--counts-only", action="store_true")
@@ -46,7 +69,7 @@ def parse(argv: list[str]) -> argparse.Namespace:
     ap.add_argument("--stats", default="", help="write run statistics to this JSON file")
     ap.add_argument("-v", dest="verbose", action="store_true")
     a = ap.parse_args(argv)
-    if math.isnan(a.radius) or a.radius < 0:
+    if a.radius is not None and (math.isnan(a.radius) or a.radius < 0):
         ap.error("-r must be >= 0")
     if a.chunk < 1:
         ap.error("--chunk must be at least 1")
@@ -86,6 +109,39 @@ def main(argv: list[str] | None = None) -> int:
     sync()
     t1 = time.perf_counter()
     nq = io.portion(a.queries, 0, 1)[2]
+    # the search of queries [b, e) of the file: one radius, one per query (sliced with the
+    # queries), or one per point (prepared once)
+    try:
+        if a.radii is not None:
+            qrad = read_radii(a.radii, "--radii", nq, a.queries)
+            if not bool((qrad >= 0).all()):
+                raise ValueError(f"--radii {a.radii}: every value must be >= 0 and not NaN")
+
+            def count_fn(q, b, e):
+                return E.radius_counts(index, q, qrad[b:e].to(dev), stats=stats, squared=a.squared)
+
+            def lists_fn(q, b, e):
+                return E.radius_neighbors(index, q, qrad[b:e].to(dev), sort=not a.unsorted, max_pairs=a.max_pairs,
+                                          squared=a.squared)
+        elif a.point_radii is not None:
+            prad = E.prepare_point_radii(index, read_radii(a.point_radii, "--point-radii", index.n, a.points).to(dev),
+                                         squared=a.squared)
+
+            def count_fn(q, b, e):
+                return E.point_radius_counts(index, q, prad, stats=stats)
+
+            def lists_fn(q, b, e):
+                return E.point_radius_neighbors(index, q, prad, sort=not a.unsorted, max_pairs=a.max_pairs)
+        else:
+            def count_fn(q, b, e):
+                return E.radius_counts(index, q, a.radius, stats=stats, squared=a.squared)
+
+            def lists_fn(q, b, e):
+                return E.radius_neighbors(index, q, a.radius, sort=not a.unsorted, max_pairs=a.max_pairs,
+                                          squared=a.squared)
+    except ValueError as e:
+        sys.stderr.write(f"hipKNN_radius: {e}\n")
+        return 1
     lists = not a.counts_only
     io.write_array(a.out + ".count", torch.empty(0, dtype=torch.int32), 0, truncate=True, total=nq)
     if lists:
@@ -95,7 +151,7 @@ def main(argv: list[str] | None = None) -> int:
     pairs = 0  # pairs written so far = the global offset of the next row
     for begin in range(0, nq, a.chunk):
         q = io.read_range(a.queries, begin, min(a.chunk, nq - begin), pin_memory=gpu).to(dev)
-        counts = E.radius_counts(index, q, a.radius, stats=stats).cpu()
+        counts = count_fn(q, begin, begin + q.shape[0]).cpu()
         io.write_array(a.out + ".count", counts, begin, truncate=False)
         if not lists:
             pairs += int(counts.sum())
@@ -108,8 +164,7 @@ def main(argv: list[str] | None = None) -> int:
                              f"more than --max-pairs {a.max_pairs}\n")
             return 1
         for s, e in runs:
-            offsets, idx, dist = E.radius_neighbors(index, q[s:e], a.radius, sort=not a.unsorted,
-                                                    max_pairs=a.max_pairs)
+            offsets, idx, dist = lists_fn(q[s:e], begin + s, begin + e)
             io.write_array(a.out + ".offsets", offsets[:-1].cpu() + pairs, begin + s, truncate=False)
             io.write_array(a.out + ".ids", idx, pairs, truncate=False)
             io.write_array(a.out + ".dist", dist, pairs, truncate=False)
@@ -122,10 +177,15 @@ def main(argv: list[str] | None = None) -> int:
         print(f"index of {index.n} points: {t1 - t0:.3f}s; {nq} queries, {pairs} pairs: {t2 - t1:.3f}s  "
               f"{nq / max(t2 - t1, 1e-9) / 1e6:.1f} Mqueries/s  kernels {E.kernels_used()}", flush=True)
     if a.stats:
+        rec = {"n": index.n, "nq": nq, "radius": a.radius, "pairs": pairs, "chunk": a.chunk,
+               "max_pairs": a.max_pairs, "device": str(dev), "index_s": t1 - t0, "query_s": t2 - t1,
+               "kernels": E.kernels_used(), "radius_search": stats.counters}
+        if a.radius is None:
+            rec.update({"radii": a.radii, "point_radii": a.point_radii})
+        if a.squared:
+            rec["squared"] = True
         with open(a.stats, "w") as f:
-            json.dump({"n": index.n, "nq": nq, "radius": a.radius, "pairs": pairs, "chunk": a.chunk,
-                       "max_pairs": a.max_pairs, "device": str(dev), "index_s": t1 - t0, "query_s": t2 - t1,
-                       "kernels": E.kernels_used(), "radius_search": stats.counters}, f, indent=1)
+            json.dump(rec, f, indent=1)
     return 0
 
 

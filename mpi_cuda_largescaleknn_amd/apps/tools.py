@@ -8,8 +8,8 @@
            [--neighbors PREFIX]  (also PREFIX.ids / PREFIX.dist of hipKNN_query --neighbors)
            -> exact CPU oracle on sampled points, bitwise compare (replaces the reference's
               disabled '#if 0' RES dump, unorderedDataVariant.cu:215-227)
-    python -m mpi_cuda_largescaleknn_amd.apps.tools rcheck in.float3 q.float3 -r R PREFIX [--samples S]
-           [--counts-only] [--unsorted]
+    python -m mpi_cuda_largescaleknn_amd.apps.tools rcheck in.float3 q.float3 PREFIX [--samples S]
+           (-r R | --radii FILE | --point-radii FILE) [--squared] [--counts-only] [--unsorted]
            -> hipKNN_radius' PREFIX.count (and .offsets / .ids / .dist) for q.float3 against the
               brute-force oracle: every count's consistency with the offsets, sampled rows bitwise
     python -m mpi_cuda_largescaleknn_amd.apps.tools cat prefix P out.float  (concatenate per-rank outputs)
@@ -21,6 +21,7 @@ import argparse
 import math
 import sys
 
+import numpy as np
 import torch
 
 from ..models.knn_engine import cut2_of
@@ -115,14 +116,34 @@ def rcheck(a) -> int:
     pts = io.read_points(a.inp)
     qry = io.read_points(a.queries)
     nq = qry.shape[0]
-    cut2 = cut2_of(a.r)
+    # the oracle of the sampled queries idx: (counts, lists) under the option given
+    if a.radius is not None:
+        cut2 = float(np.float32(a.radius)) if a.squared else cut2_of(a.radius)
+
+        def oracle(idx):
+            return K.radius_count_cpu(pts, qry[idx], cut2), lambda: K.radius_cpu(pts, qry[idx], cut2)
+    else:
+        from .radius import read_radii
+        try:
+            if a.radii is not None:
+                rad = read_radii(a.radii, "--radii", nq, a.queries)
+            else:
+                rad = read_radii(a.point_radii, "--point-radii", pts.shape[0], a.inp)
+        except ValueError as e:
+            print(e)
+            return 1
+        c2 = rad if a.squared else rad * rad
+
+        def oracle(idx):
+            qc, pc = (c2[idx], None) if a.radii is not None else (None, c2)
+            return K.radius_var_count_cpu(pts, qry[idx], qc, pc), lambda: K.radius_var_cpu(pts, qry[idx], qc, pc)
     counts = io.read_array(a.prefix + ".count", torch.int32)
     if counts.shape[0] != nq:
         print(f"size mismatch: {counts.shape[0]} counts for {nq} queries")
         return 1
     g = torch.Generator().manual_seed(0)
     idx = torch.randint(0, nq, (min(a.samples, nq),), generator=g) if a.samples < nq else torch.arange(nq)
-    ref_c = K.radius_count_cpu(pts, qry[idx], cut2)
+    ref_c, ref_lists = oracle(idx)
     wrong = counts[idx] != ref_c
     bad = int(wrong.sum())
     print(f"checked {idx.numel()} sampled counts: {bad} mismatches")
@@ -140,7 +161,7 @@ def rcheck(a) -> int:
         print(f"offsets are not the prefix sums of the counts, or ids ({ids.shape[0]}) / dist ({dist.shape[0]}) "
               f"do not hold their total of {int(want[nq])} pairs")
         return 1
-    ro, ri, rd2 = K.radius_cpu(pts, qry[idx], cut2)
+    ro, ri, rd2 = ref_lists()
     rd = K.finalize_distances(rd2)
     rows_bad = 0
     for i, qi in enumerate(idx.tolist()):
@@ -214,7 +235,8 @@ def main(argv=None) -> int:
     p.add_argument("inp")
     p.add_argument("queries")
     p.add_argument("prefix", help="the -o PREFIX of hipKNN_radius")
-    p.add_argument("-r", type=float, required=True)
+    from .radius import add_radius_options
+    add_radius_options(p)
     p.add_argument("--samples", type=int, default=1000)
     p.add_argument("--counts-only", action="store_true")
     p.add_argument("--unsorted", action="store_true", help="rows written with --unsorted: compared as sets")

@@ -232,6 +232,49 @@ extern "C" void lsk_cpu_radius_fill(const float *pts, int64_t n, const float *qr
   });
 }
 
+// Variable radii: point i is in row q iff d² < qcut2[q] (when given) and d² < pcut2[i] (when
+// given).
+extern "C" void lsk_cpu_radius_var_count(const float *pts, int64_t n, const float *qry, int64_t nq,
+                                         const float *qcut2, const float *pcut2, int32_t *counts, int nthreads) {
+  const vec3f *P = (const vec3f *)pts;
+  const vec3f *Q = (const vec3f *)qry;
+  parallel_for(nq, nthreads, [&](int64_t b, int64_t e) {
+    for (int64_t qi = b; qi < e; qi++) {
+      int32_t c = 0;
+      for (int64_t i = 0; i < n; i++) {
+        const float v = lsk::dist2(Q[qi], P[i]);
+        c += (!qcut2 || v < qcut2[qi]) && (!pcut2 || v < pcut2[i]);
+      }
+      counts[qi] = c;
+    }
+  });
+}
+
+extern "C" void lsk_cpu_radius_var_fill(const float *pts, int64_t n, const float *qry, int64_t nq,
+                                        const float *qcut2, const float *pcut2, const int64_t *offsets,
+                                        int32_t *out_idx, float *out_d2, int nthreads) {
+  const vec3f *P = (const vec3f *)pts;
+  const vec3f *Q = (const vec3f *)qry;
+  parallel_for(nq, nthreads, [&](int64_t b, int64_t e) {
+    std::vector<uint64_t> d;  // d2 bits << 32 | input row, as lsk_cpu_knn_brute
+    for (int64_t qi = b; qi < e; qi++) {
+      d.clear();
+      for (int64_t i = 0; i < n; i++) {
+        const float v = lsk::dist2(Q[qi], P[i]);
+        if ((!qcut2 || v < qcut2[qi]) && (!pcut2 || v < pcut2[i]))
+          d.push_back(((uint64_t)lsk::fbits(v) << 32) | (uint32_t)i);
+      }
+      std::sort(d.begin(), d.end());
+      // (offsets come from lsk_cpu_radius_var_count with the same cutoffs)
+      const size_t m = std::min<size_t>(d.size(), (size_t)(offsets[qi + 1] - offsets[qi]));
+      for (size_t j = 0; j < m; j++) {
+        out_idx[offsets[qi] + (int64_t)j] = (int32_t)(uint32_t)d[j];
+        out_d2[offsets[qi] + (int64_t)j] = lsk::bitsf((uint32_t)(d[j] >> 32));
+      }
+    }
+  });
+}
+
 extern "C" void lsk_cpu_count_below(const float *pts, int64_t n, const float *qry,
                                     const float *thr, int nq, unsigned long long *counts,
                                     int nthreads) {

@@ -90,6 +90,14 @@ void lsk_cpu_radius_count(const float *pts, int64_t n, const float *qry, int64_t
                           int32_t *counts, int nthreads);
 void lsk_cpu_radius_fill(const float *pts, int64_t n, const float *qry, int64_t nq, float cut2,
                          const int64_t *offsets, int32_t *out_idx, float *out_d2, int nthreads);
+// The same with a squared cutoff per query (qcut2 [nq], optional) and / or per point (pcut2
+// [n], optional): point i is in row q iff dist2 < qcut2[q] (when given) and dist2 < pcut2[i]
+// (when given). Same CSR form and row order.
+void lsk_cpu_radius_var_count(const float *pts, int64_t n, const float *qry, int64_t nq, const float *qcut2,
+                              const float *pcut2, int32_t *counts, int nthreads);
+void lsk_cpu_radius_var_fill(const float *pts, int64_t n, const float *qry, int64_t nq, const float *qcut2,
+                             const float *pcut2, const int64_t *offsets, int32_t *out_idx, float *out_d2,
+                             int nthreads);
 // Verification counts (= lsk_hip_count_below): counts[2j] += #{p : dist2(q_j,p) < thr[2j]},
 // counts[2j+1] += #{p : dist2(q_j,p) < thr[2j+1]}.
 void lsk_cpu_count_below(const float *pts, int64_t n, const float *qry, const float *thr, int nq,

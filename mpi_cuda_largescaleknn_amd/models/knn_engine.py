@@ -1039,18 +1039,140 @@ def knn_neighbors(points: torch.Tensor, k: int, max_radius: float = math.inf,
 LAST_RADIUS_ERRORS = [0]
 
 
-def _radius_cut2(what: str, radius: float) -> float:
+def _radius_cut2(what: str, radius: float, squared: bool = False) -> float:
     r = float(radius)
     if math.isnan(r) or r < 0.0:
         raise ValueError(f"{what}: radius must be >= 0 (got {radius})")
-    return cut2_of(r)
+    return float(np.float32(r)) if squared else cut2_of(r)
 
 
 _RADIUS_STATS = ("radius_evals", "radius_nodes", "radius_buckets", "radius_box_accepts")
 
 
-def radius_counts(index: LocalIndex, queries: torch.Tensor, radius: float, stats: KnnStats | None = None,
-                  _sorted: tuple | None = None) -> torch.Tensor:
+def _add_radius_stats(stats: KnnStats, raw: torch.Tensor) -> None:
+    for nm, v in zip(_RADIUS_STATS, raw.cpu().tolist()):
+        stats.counters[nm] = stats.counters.get(nm, 0) + int(v)
+
+
+def _empty_csr(nq: int, dev: torch.device) -> tuple:
+    return (torch.zeros(nq + 1, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int32, device=dev),
+            torch.empty(0, dtype=torch.float32, device=dev))
+
+
+# ---- variable radii: one per query (gather) or one per indexed point (scatter)
+def _cut2_tensor(what: str, name: str, radii: torch.Tensor, count: int, device: torch.device,
+                 squared: bool) -> torch.Tensor:
+    """The float32 [count] squared cutoffs of a radius tensor (`squared`: the tensor itself).
+    Wrong type, shape or device, or an entry that is negative or NaN: ValueError (one small
+    device reduction is read for the last)."""
+    if not isinstance(radii, torch.Tensor) or radii.dtype != torch.float32 or radii.dim() != 1 \
+            or radii.shape[0] != count:
+        got = f"{radii.dtype} {tuple(radii.shape)}" if isinstance(radii, torch.Tensor) else type(radii).__name__
+        raise ValueError(f"{what}: {name} must be a float32 [{count}] tensor (got {got})")
+    if radii.device != device:
+        raise ValueError(f"{what}: {name} on {radii.device}, the index on {device}")
+    r = radii.contiguous()
+    if count and not bool((r >= 0).all()):  # (a NaN fails the comparison too)
+        raise ValueError(f"{what}: every entry of {name} must be >= 0 and not NaN")
+    return r if squared else r * r
+
+
+@dataclass
+class PointRadii:
+    """Per-point radii prepared for one index (prepare_point_radii)."""
+    index: LocalIndex
+    cut2: torch.Tensor                  # float32 [n] squared cutoffs, rows of the indexed array
+    cut2_sorted: torch.Tensor | None    # GPU index: the same in the index's curve order
+    nodes: torch.Tensor | None          # GPU index: copy of index.nodes, lo.w = largest cut2 below the node
+
+
+def prepare_point_radii(index: LocalIndex, point_radii: torch.Tensor, squared: bool = False) -> PointRadii:
+    """Per-point radii (float32 [n] on the index's device, in the order of the indexed array's
+    rows; `squared`: squared cutoffs) made ready for the point_radius_* searches over
+    `index`: the cutoffs in curve order and a private copy of the node array annotated with
+    the largest cutoff below every node. The index itself is not written. Every point_radius_*
+    function that takes an index accepts the result in place of the tensor, so a caller that
+    sends queries in chunks prepares the radii once."""
+    cut2 = _cut2_tensor("prepare_point_radii", "point_radii", point_radii, index.n, index.device, squared)
+    if not K.is_gpu(index.pts) or index.n == 0:
+        return PointRadii(index, cut2, None, None)
+    cut2_sorted = cut2[index.perm[:index.n].long()].contiguous()
+    nodes = index.nodes.clone()
+    K.tree_set_radii(nodes, index.n, cut2_sorted)
+    return PointRadii(index, cut2, cut2_sorted, nodes)
+
+
+def _point_radii(what: str, index: LocalIndex, point_radii, squared: bool) -> PointRadii:
+    if isinstance(point_radii, PointRadii):
+        if point_radii.index is not index:
+            raise ValueError(f"{what}: the point radii were prepared for another index")
+        return point_radii
+    try:
+        return prepare_point_radii(index, point_radii, squared)
+    except ValueError as e:
+        raise ValueError(str(e).replace("prepare_point_radii", what, 1)) from None
+
+
+def _var_counts(what: str, index: LocalIndex, queries: torch.Tensor, qcut2: torch.Tensor | None,
+                prad: PointRadii | None, stats: KnnStats | None, _sorted: tuple | None = None) -> torch.Tensor:
+    """radius_counts with cutoffs per query (qcut2) or per point (prad); checked arguments."""
+    nq, n = queries.shape[0], index.n
+    if nq == 0 or n == 0:
+        return torch.zeros(nq, dtype=torch.int32, device=index.device)
+    if not K.is_gpu(index.pts):
+        KERNELS_USED.add("cpu")
+        if prad is None:
+            return K.radius_var_count_cpu(index.pts[:n], queries, qcut2, None)
+        return K.radius_var_count_cpu(_input_order(index), queries, None, prad.cut2)
+    qsorted, qperm = _sorted if _sorted is not None else prepare_queries(index, queries, locate=False)[:2]
+    raw = torch.zeros(4, dtype=torch.int64, device=index.device) if stats is not None else None
+    if prad is None:
+        counts = K.radius_var_count_gpu(index.tree(), qsorted, nq, qperm, qcut2=qcut2, stats=raw)
+    else:
+        tree = (index.pts, prad.nodes, index.qnodes, n, index.depth)
+        counts = K.radius_var_count_gpu(tree, qsorted, nq, qperm, pcut2=prad.cut2_sorted, stats=raw)
+    KERNELS_USED.add("radius_var")
+    if stats is not None:
+        _add_radius_stats(stats, raw)
+    return counts
+
+
+def _var_neighbors(what: str, index: LocalIndex, queries: torch.Tensor, qcut2: torch.Tensor | None,
+                   prad: PointRadii | None, sort: bool, max_pairs: int) -> tuple:
+    """radius_neighbors with cutoffs per query (qcut2) or per point (prad); checked arguments."""
+    nq, n = queries.shape[0], index.n
+    dev = index.device
+    gpu = K.is_gpu(index.pts)
+    if nq == 0 or n == 0:
+        return _empty_csr(nq, dev)
+    prep = prepare_queries(index, queries, locate=False)[:2] if gpu else None
+    counts = _var_counts(what, index, queries, qcut2, prad, None, _sorted=prep)
+    offsets = torch.zeros(nq + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, dtype=torch.int64, out=offsets[1:])
+    total, longest = (int(v) for v in torch.stack((offsets[nq], counts.max().long())).tolist())  # the only sync
+    if total > max_pairs:
+        raise ValueError(f"{what}: {total} pairs within the radii exceed max_pairs = {max_pairs}; "
+                         "query fewer points at a time or raise max_pairs")
+    if not gpu:
+        o2, idx, d2 = K.radius_var_cpu(_input_order(index), queries, qcut2, None if prad is None else prad.cut2)
+        return o2, idx, K.finalize_distances(d2)
+    qsorted, qperm = prep
+    if prad is None:
+        idx, dist, err = K.radius_var_fill_gpu(index.tree(), index.perm, qsorted, nq, qperm, offsets, total, longest,
+                                               qcut2=qcut2, sort=sort)
+    else:
+        tree = (index.pts, prad.nodes, index.qnodes, n, index.depth)
+        idx, dist, err = K.radius_var_fill_gpu(tree, index.perm, qsorted, nq, qperm, offsets, total, longest,
+                                               pcut2=prad.cut2_sorted, sort=sort)
+    LAST_RADIUS_ERRORS[0] = int(err.item()) & 0xFFFFFFFF
+    if LAST_RADIUS_ERRORS[0]:
+        raise NativeError(f"{what}: {LAST_RADIUS_ERRORS[0]} rows were not filled to their count "
+                          "(the count pass and the fill pass disagree: a bug)")
+    return offsets, idx, dist
+
+
+def radius_counts(index: LocalIndex, queries: torch.Tensor, radius: float | torch.Tensor,
+                  stats: KnnStats | None = None, _sorted: tuple | None = None, squared: bool = False) -> torch.Tensor:
     """int32 [nq], in query order: for every row of `queries` (float32 [nq, 3] on the index's
     device) the number of points of `index` with dist2(q, p) < cut2_of(radius) — the strict
     comparison of the k-th-distance cutoff, so count >= k exactly when query_points with that
@@ -1058,8 +1180,17 @@ def radius_counts(index: LocalIndex, queries: torch.Tensor, radius: float, stats
     radius = inf every point; a query with a NaN or infinite coordinate counts nothing. Boxes
     that lie wholly inside a query's ball are counted without visiting their points, so large
     radii cost far less than n distance evaluations per query. `stats` receives
-    radius_evals / radius_nodes / radius_buckets / radius_box_accepts."""
-    cut2 = _radius_cut2("radius_counts", radius)
+    radius_evals / radius_nodes / radius_buckets / radius_box_accepts.
+
+    `radius` may be a float32 tensor [nq] on the index's device, one radius per query row
+    (gather: p counts for q iff dist2(q, p) < cut2[q]); a negative or NaN entry raises
+    ValueError before any kernel runs. squared=True: the given value(s) are the squared
+    cutoffs themselves (the engine's own squared distances can be handed back as they are)."""
+    if isinstance(radius, torch.Tensor):
+        queries = _check_foreign("radius_counts", index, queries)
+        qcut2 = _cut2_tensor("radius_counts", "radius", radius, queries.shape[0], index.device, squared)
+        return _var_counts("radius_counts", index, queries, qcut2, None, stats, _sorted=_sorted)
+    cut2 = _radius_cut2("radius_counts", radius, squared)
     queries = _check_foreign("radius_counts", index, queries)
     nq, n = queries.shape[0], index.n
     if nq == 0 or n == 0:
@@ -1077,25 +1208,30 @@ def radius_counts(index: LocalIndex, queries: torch.Tensor, radius: float, stats
     return counts
 
 
-def radius_neighbors(index: LocalIndex, queries: torch.Tensor, radius: float, sort: bool = True,
-                     max_pairs: int = 1 << 28) -> tuple:
+def radius_neighbors(index: LocalIndex, queries: torch.Tensor, radius: float | torch.Tensor, sort: bool = True,
+                     max_pairs: int = 1 << 28, squared: bool = False) -> tuple:
     """Fixed-radius neighbour lists in CSR form, in query order: (offsets int64 [nq + 1], idx
     int32 [total], dist float32 [total]). Row q = [offsets[q], offsets[q + 1]) holds every
     point of `index` with dist2(q, p) < cut2_of(radius) (see radius_counts), however many
     there are: idx are rows of the indexed array, dist the final distances. sort=True: each
     row ascending by (dist2 bits, row), the order of the neighbour lists, whatever the
     index's internal order; sort=False: unspecified order inside a row (cheaper). More than
-    `max_pairs` pairs in all raise ValueError before anything is allocated for them."""
-    cut2 = _radius_cut2("radius_neighbors", radius)
+    `max_pairs` pairs in all raise ValueError before anything is allocated for them.
+    `radius` may be a float32 tensor [nq], one radius per query row; `squared` as in
+    radius_counts."""
+    if isinstance(radius, torch.Tensor):
+        queries = _check_foreign("radius_neighbors", index, queries)
+        qcut2 = _cut2_tensor("radius_neighbors", "radius", radius, queries.shape[0], index.device, squared)
+        return _var_neighbors("radius_neighbors", index, queries, qcut2, None, sort, max_pairs)
+    cut2 = _radius_cut2("radius_neighbors", radius, squared)
     queries = _check_foreign("radius_neighbors", index, queries)
     nq, n = queries.shape[0], index.n
     dev = index.device
     gpu = K.is_gpu(index.pts)
     if nq == 0 or n == 0:
-        return (torch.zeros(nq + 1, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int32, device=dev),
-                torch.empty(0, dtype=torch.float32, device=dev))
+        return _empty_csr(nq, dev)
     prep = prepare_queries(index, queries, locate=False)[:2] if gpu else None
-    counts = radius_counts(index, queries, radius, _sorted=prep)
+    counts = radius_counts(index, queries, radius, _sorted=prep, squared=squared)
     offsets = torch.zeros(nq + 1, dtype=torch.int64, device=dev)
     torch.cumsum(counts, 0, dtype=torch.int64, out=offsets[1:])
     total, longest = (int(v) for v in torch.stack((offsets[nq], counts.max().long())).tolist())  # the only sync
@@ -1115,33 +1251,92 @@ def radius_neighbors(index: LocalIndex, queries: torch.Tensor, radius: float, so
     return offsets, idx, dist
 
 
-def radius_query_counts(points: torch.Tensor, queries: torch.Tensor, radius: float,
-                        stats: KnnStats | None = None) -> torch.Tensor:
+def _check_radius(what: str, radius, nq: int, device: torch.device, squared: bool) -> None:
+    """The checks of a scalar or per-query radius where nothing is searched (no points)."""
+    if isinstance(radius, torch.Tensor):
+        _cut2_tensor(what, "radius", radius, nq, device, squared)
+    else:
+        _radius_cut2(what, radius, squared)
+
+
+def radius_query_counts(points: torch.Tensor, queries: torch.Tensor, radius: float | torch.Tensor,
+                        stats: KnnStats | None = None, squared: bool = False) -> torch.Tensor:
     """radius_counts over an index built once from `points` (both float32 [*, 3] on one
     device), in the points' own frame."""
     if points.device != queries.device:
         raise ValueError(f"radius_query_counts: points on {points.device}, queries on {queries.device}")
     if points.shape[0] == 0:  # nothing to index
-        _radius_cut2("radius_query_counts", radius)
+        _check_radius("radius_query_counts", radius, queries.shape[0], queries.device, squared)
         return torch.zeros(queries.shape[0], dtype=torch.int32, device=queries.device)
-    return radius_counts(build_index(points), queries, radius, stats=stats)
+    return radius_counts(build_index(points), queries, radius, stats=stats, squared=squared)
 
 
-def radius_query_neighbors(points: torch.Tensor, queries: torch.Tensor, radius: float, sort: bool = True,
-                           max_pairs: int = 1 << 28) -> tuple:
+def radius_query_neighbors(points: torch.Tensor, queries: torch.Tensor, radius: float | torch.Tensor,
+                           sort: bool = True, max_pairs: int = 1 << 28, squared: bool = False) -> tuple:
     """radius_neighbors over an index built once from `points`, in the points' own frame."""
     if points.device != queries.device:
         raise ValueError(f"radius_query_neighbors: points on {points.device}, queries on {queries.device}")
     if points.shape[0] == 0:  # nothing to index: every row is empty
-        _radius_cut2("radius_query_neighbors", radius)
-        dev = queries.device
-        return (torch.zeros(queries.shape[0] + 1, dtype=torch.int64, device=dev),
-                torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.float32, device=dev))
-    return radius_neighbors(build_index(points), queries, radius, sort=sort, max_pairs=max_pairs)
+        _check_radius("radius_query_neighbors", radius, queries.shape[0], queries.device, squared)
+        return _empty_csr(queries.shape[0], queries.device)
+    return radius_neighbors(build_index(points), queries, radius, sort=sort, max_pairs=max_pairs, squared=squared)
 
 
-def radius_self_neighbors(points: torch.Tensor, radius: float, sort: bool = True, max_pairs: int = 1 << 28) -> tuple:
+def radius_self_neighbors(points: torch.Tensor, radius: float | torch.Tensor, sort: bool = True,
+                          max_pairs: int = 1 << 28, squared: bool = False) -> tuple:
     """radius_query_neighbors with the points as their own queries: for radius > 0 every
     sorted row starts with a point at distance 0 (itself, or the lowest row among its
     exact copies)."""
-    return radius_query_neighbors(points, points, radius, sort=sort, max_pairs=max_pairs)
+    return radius_query_neighbors(points, points, radius, sort=sort, max_pairs=max_pairs, squared=squared)
+
+
+def point_radius_counts(index: LocalIndex, queries: torch.Tensor, point_radii, squared: bool = False,
+                        stats: KnnStats | None = None) -> torch.Tensor:
+    """int32 [nq], in query order: for every row of `queries` the number of points p of
+    `index` whose own ball reaches it, dist2(q, p) < cut2[p] (scatter: "which points reach
+    me"). point_radii: float32 [n] on the index's device in the order of the indexed array's
+    rows (squared=True: squared cutoffs), or the result of prepare_point_radii for this
+    index. A radius of 0 selects nothing, a point with radius inf is counted by every finite
+    query; a negative or NaN entry raises ValueError before any kernel runs. The walk culls a
+    node with the largest cutoff below it; there is no whole-box shortcut (it would need the
+    smallest cutoff below a node), so radius_box_accepts stays 0 in `stats`."""
+    queries = _check_foreign("point_radius_counts", index, queries)
+    prad = _point_radii("point_radius_counts", index, point_radii, squared)
+    return _var_counts("point_radius_counts", index, queries, None, prad, stats)
+
+
+def point_radius_neighbors(index: LocalIndex, queries: torch.Tensor, point_radii, squared: bool = False,
+                           sort: bool = True, max_pairs: int = 1 << 28) -> tuple:
+    """The CSR lists of radius_neighbors under the per-point predicate of point_radius_counts:
+    row q holds every point p of `index` with dist2(q, p) < cut2[p], in the same order."""
+    queries = _check_foreign("point_radius_neighbors", index, queries)
+    prad = _point_radii("point_radius_neighbors", index, point_radii, squared)
+    return _var_neighbors("point_radius_neighbors", index, queries, None, prad, sort, max_pairs)
+
+
+def _point_query_index(what: str, points: torch.Tensor, queries: torch.Tensor) -> LocalIndex:
+    if points.device != queries.device:
+        raise ValueError(f"{what}: points on {points.device}, queries on {queries.device}")
+    return build_index(points)
+
+
+def point_radius_query_counts(points: torch.Tensor, queries: torch.Tensor, point_radii: torch.Tensor,
+                              squared: bool = False, stats: KnnStats | None = None) -> torch.Tensor:
+    """point_radius_counts over an index built once from `points`, in the points' own frame."""
+    index = _point_query_index("point_radius_query_counts", points, queries)
+    return point_radius_counts(index, queries, point_radii, squared=squared, stats=stats)
+
+
+def point_radius_query_neighbors(points: torch.Tensor, queries: torch.Tensor, point_radii: torch.Tensor,
+                                 squared: bool = False, sort: bool = True, max_pairs: int = 1 << 28) -> tuple:
+    """point_radius_neighbors over an index built once from `points`, in the points' own frame."""
+    index = _point_query_index("point_radius_query_neighbors", points, queries)
+    return point_radius_neighbors(index, queries, point_radii, squared=squared, sort=sort, max_pairs=max_pairs)
+
+
+def point_radius_self_neighbors(points: torch.Tensor, point_radii: torch.Tensor, squared: bool = False,
+                                sort: bool = True, max_pairs: int = 1 << 28) -> tuple:
+    """point_radius_query_neighbors with the points as their own queries: row i holds the
+    points whose ball contains point i (with the k-th squared distances as squared radii, the
+    points that have i among their k nearest, ties at the k-th distance left out)."""
+    return point_radius_query_neighbors(points, points, point_radii, squared=squared, sort=sort, max_pairs=max_pairs)

@@ -691,6 +691,97 @@ def radius_cpu(points: torch.Tensor, queries: torch.Tensor, cut2: float) -> tupl
     return offsets, idx, d2
 
 
+def _var_cut2_cpu(what: str, cut2: torch.Tensor | None, count: int) -> torch.Tensor | None:
+    if cut2 is None:
+        return None
+    c = cut2.contiguous().float().cpu()
+    if c.shape != (count,):
+        raise ValueError(f"{what}: {tuple(c.shape)} cutoffs for {count} rows")
+    return c
+
+
+def radius_var_count_cpu(points: torch.Tensor, queries: torch.Tensor, qcut2: torch.Tensor | None = None,
+                         pcut2: torch.Tensor | None = None) -> torch.Tensor:
+    """CPU oracle (brute force) of the variable-radius counts: int32 [nq], per query q the
+    number of rows p of `points` with dist2 < qcut2[q] (float32 [nq], when given) and dist2 <
+    pcut2[p] (float32 [n], in the order of `points`, when given); strict."""
+    pts = points.contiguous().float().cpu()
+    q = queries.contiguous().float().cpu()
+    qc = _var_cut2_cpu("radius_var_count_cpu", qcut2, q.shape[0])
+    pc = _var_cut2_cpu("radius_var_count_cpu", pcut2, pts.shape[0])
+    counts = torch.empty(q.shape[0], dtype=torch.int32)
+    _native.host().lsk_cpu_radius_var_count(_ptr(pts), pts.shape[0], _ptr(q), q.shape[0], _ptr(qc), _ptr(pc),
+                                            _ptr(counts), _nthreads())
+    return counts
+
+
+def radius_var_cpu(points: torch.Tensor, queries: torch.Tensor, qcut2: torch.Tensor | None = None,
+                   pcut2: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """CPU oracle of the variable-radius lists (brute force), the CSR form and row order of
+    radius_cpu under the predicate of radius_var_count_cpu."""
+    pts = points.contiguous().float().cpu()
+    q = queries.contiguous().float().cpu()
+    qc = _var_cut2_cpu("radius_var_cpu", qcut2, q.shape[0])
+    pc = _var_cut2_cpu("radius_var_cpu", pcut2, pts.shape[0])
+    nq = q.shape[0]
+    offsets = torch.zeros(nq + 1, dtype=torch.int64)
+    torch.cumsum(radius_var_count_cpu(pts, q, qc, pc), 0, dtype=torch.int64, out=offsets[1:])
+    total = int(offsets[nq])
+    idx = torch.empty(total, dtype=torch.int32)
+    d2 = torch.empty(total, dtype=torch.float32)
+    _native.host().lsk_cpu_radius_var_fill(_ptr(pts), pts.shape[0], _ptr(q), nq, _ptr(qc), _ptr(pc), _ptr(offsets),
+                                           _ptr(idx), _ptr(d2), _nthreads())
+    return offsets, idx, d2
+
+
+def _radius_var_args(what: str, tree: tuple, qsorted: torch.Tensor, nq: int, out_perm: torch.Tensor,
+                     qcut2: torch.Tensor | None, pcut2: torch.Tensor | None):
+    if (qcut2 is None) == (pcut2 is None):
+        raise ValueError(f"{what}: exactly one of qcut2 and pcut2")
+    t, cnt = (qcut2, nq) if qcut2 is not None else (pcut2, tree[3])
+    if t.dtype != torch.float32 or t.shape != (cnt,) or not t.is_contiguous() or t.device != tree[0].device:
+        raise ValueError(f"{what}: cutoffs float32 [{cnt}], contiguous, on the tree's device")
+    return _walk_view(what, tree, qsorted, nq, out_perm)
+
+
+def radius_var_count_gpu(tree: tuple, qsorted: torch.Tensor, nq: int, out_perm: torch.Tensor,
+                         qcut2: torch.Tensor | None = None, pcut2: torch.Tensor | None = None,
+                         stats: torch.Tensor | None = None) -> torch.Tensor:
+    """The count pass of the variable-radius search (radius_var.hip), as radius_count_gpu.
+    qcut2: float32 [nq] squared cutoffs in query order (gather), or pcut2: float32 [n] in the
+    order of the tree's sorted points (scatter), the tree's node array then being a copy
+    annotated with them (tree_set_radii). Entries >= 0, no NaN: the caller checks."""
+    tv = _radius_var_args("radius_var_count_gpu", tree, qsorted, nq, out_perm, qcut2, pcut2)
+    counts = torch.empty(nq, dtype=torch.int32, device=tree[0].device)
+    check(_native.hip().lsk_hip_radius_var_count(C.byref(tv), _ptr(qsorted), int(nq), _ptr(qcut2), _ptr(pcut2),
+                                                 _ptr(out_perm), _ptr(counts), _ptr(stats), _stream(tree[0])),
+          "radius_var_count")
+    return counts
+
+
+def radius_var_fill_gpu(tree: tuple, perm: torch.Tensor, qsorted: torch.Tensor, nq: int, out_perm: torch.Tensor,
+                        offsets: torch.Tensor, total: int, longest: int, qcut2: torch.Tensor | None = None,
+                        pcut2: torch.Tensor | None = None,
+                        sort: bool = True) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The fill and sort passes of the variable-radius search, as radius_fill_gpu (the sort
+    is lsk_hip_radius_sort itself); cutoffs as for radius_var_count_gpu."""
+    tv = _radius_var_args("radius_var_fill_gpu", tree, qsorted, nq, out_perm, qcut2, pcut2)
+    dev = tree[0].device
+    if offsets.dtype != torch.int64 or offsets.numel() != nq + 1 or not offsets.is_contiguous() or offsets.device != dev \
+            or perm.dtype != torch.int32 or perm.numel() < tree[3] or not perm.is_contiguous() or perm.device != dev:
+        raise ValueError("radius_var_fill_gpu: offsets int64 [nq + 1] and perm int32 [n], contiguous, on the tree's device")
+    lib = _native.hip()
+    idx = torch.empty(total, dtype=torch.int32, device=dev)
+    dist = torch.empty(total, dtype=torch.float32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    check(lib.lsk_hip_radius_var_fill(C.byref(tv), _ptr(perm), _ptr(qsorted), int(nq), _ptr(qcut2), _ptr(pcut2),
+                                      _ptr(out_perm), _ptr(offsets), _ptr(idx), _ptr(dist), _ptr(err),
+                                      _stream(tree[0])), "radius_var_fill")
+    check(lib.lsk_hip_radius_sort(_ptr(offsets), int(nq), int(total), int(longest), _ptr(idx), _ptr(dist),
+                                  1 if sort else 0, _stream(tree[0])), "radius_sort")
+    return idx, dist, err
+
+
 def _radius_args(what: str, tree: tuple, qsorted: torch.Tensor, nq: int, cut2: float, out_perm: torch.Tensor):
     if not cut2 >= 0.0:
         raise ValueError(f"{what}: cut2 must be >= 0")

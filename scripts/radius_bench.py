@@ -2,6 +2,7 @@
 """Fixed-radius search throughput on one GPU, beside the k-nearest lists of the same size.
 
     python scripts/radius_bench.py [--points 1e7] [--queries 1e6] [--mean 100] [--steps 5] [--warmup 2]
+                                   [--radii scalar|query-equal|query-loguniform|query-kth|point-kth]
 
 Uniform points in the unit cube and uniform queries from another seed; the radius is the one
 whose ball holds --mean points at the data's density (queries near the faces see fewer, so
@@ -13,6 +14,12 @@ step so that drift on a shared host hits them alike:
   * unsorted:  radius_neighbors(sort=False);
   * knn_lists: query_neighbors at k = --mean on the same index and queries — the yardstick:
                lists of the same size that need a selection pass first.
+--radii selects what the three radius cases search with (default scalar: one radius r):
+  * query-equal:      a per-query tensor filled with r (the gather kernels on the scalar's work);
+  * query-loguniform: per-query radii log-uniform in [r / 8, 2 r];
+  * query-kth:        per-query radii 1.3 x the query's k-th neighbour distance, k = --kth;
+  * point-kth:        per-point radii = every point's own k-th neighbour distance (scatter:
+                      the reverse-neighbour search), prepared once outside the timed region.
 Prints one JSON line. Sampled rows are checked against brute force.
 """
 from __future__ import annotations
@@ -41,6 +48,9 @@ def main() -> int:
     ap.add_argument("--mean", type=int, default=100, help="mean neighbours per query, and the yardstick's k")
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--radii", default="scalar",
+                    choices=["scalar", "query-equal", "query-loguniform", "query-kth", "point-kth"])
+    ap.add_argument("--kth", type=int, default=32, help="k of the k-th-distance radii (query-kth, point-kth)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.stderr.write("radius_bench: needs a GPU (a CPU timing says nothing about it)\n")
@@ -54,10 +64,32 @@ def main() -> int:
     E.bucket_keys(index)
     cfg = E.KnnConfig(k=k)
     out = {}
+    # what the radius cases search with: (counts, lists) functions and the oracle's cutoffs
+    qc2 = pc2 = None
+    if a.radii == "point-kth":
+        pr = E.knn_distances(p, a.kth)
+        prad = E.prepare_point_radii(index, pr)
+        pc2 = pr * pr
+        counts_fn = lambda: E.point_radius_counts(index, q, prad)  # noqa: E731
+        lists_fn = lambda sort=True: E.point_radius_neighbors(index, q, prad, sort=sort)  # noqa: E731
+    else:
+        if a.radii == "scalar":
+            rad = r
+        elif a.radii == "query-equal":
+            rad = torch.full((nq,), r, device=dev)
+        elif a.radii == "query-loguniform":
+            u = torch.rand(nq, generator=torch.Generator(device=dev).manual_seed(4), device=dev)
+            rad = torch.exp(math.log(r / 8) + math.log(16.0) * u)
+        else:
+            rad = 1.3 * E.query_points(index, q, E.KnnConfig(k=a.kth))
+        if a.radii != "scalar":
+            qc2 = rad * rad
+        counts_fn = lambda: E.radius_counts(index, q, rad)  # noqa: E731
+        lists_fn = lambda sort=True: E.radius_neighbors(index, q, rad, sort=sort)  # noqa: E731
     cases = {
-        "counts": lambda: out.__setitem__("counts", E.radius_counts(index, q, r)),
-        "sorted": lambda: out.__setitem__("sorted", E.radius_neighbors(index, q, r)),
-        "unsorted": lambda: out.__setitem__("unsorted", E.radius_neighbors(index, q, r, sort=False)),
+        "counts": lambda: out.__setitem__("counts", counts_fn()),
+        "sorted": lambda: out.__setitem__("sorted", lists_fn()),
+        "unsorted": lambda: out.__setitem__("unsorted", lists_fn(sort=False)),
         "knn_lists": lambda: out.__setitem__("knn", E.query_neighbors(index, q, cfg)),
     }
     times = {name: [] for name in cases}
@@ -72,11 +104,15 @@ def main() -> int:
                 times[name].append(time.perf_counter() - t0)
     med = {name: statistics.median(ts) for name, ts in times.items()}
 
-    offsets, idx, dist = E.radius_neighbors(index, q, r)
-    counts = E.radius_counts(index, q, r)
+    offsets, idx, dist = lists_fn()
+    counts = counts_fn()
     total = int(offsets[-1])
     smp = torch.randint(0, nq, (64,), generator=torch.Generator().manual_seed(3))
-    ro, ri, rd2 = K.radius_cpu(p.cpu(), q[smp.to(dev)].cpu(), E.cut2_of(r))
+    if a.radii == "scalar":
+        ro, ri, rd2 = K.radius_cpu(p.cpu(), q[smp.to(dev)].cpu(), E.cut2_of(r))
+    else:
+        ro, ri, rd2 = K.radius_var_cpu(p.cpu(), q[smp.to(dev)].cpu(), None if qc2 is None else qc2[smp.to(dev)].cpu(),
+                                       None if pc2 is None else pc2.cpu())
     rd = K.finalize_distances(rd2)
     off = offsets.cpu()
     exact = 0
@@ -85,7 +121,7 @@ def main() -> int:
         exact += int(torch.equal(gi, ri[ro[j]:ro[j + 1]]) and torch.equal(gd, rd[ro[j]:ro[j + 1]]))
     consistent = bool(torch.equal(torch.cumsum(counts, 0, dtype=torch.int64), offsets[1:]))
     rec = {
-        "points": n, "queries": nq, "radius": r, "mean_count": total / nq, "max_count": int(counts.max()),
+        "points": n, "queries": nq, "radii": a.radii, "radius": r, "mean_count": total / nq, "max_count": int(counts.max()),
         "pairs": total, "steps": a.steps, "warmup": a.warmup,
         "counts_s": med["counts"], "sorted_s": med["sorted"], "unsorted_s": med["unsorted"],
         "knn_lists_k": k, "knn_lists_s": med["knn_lists"],
