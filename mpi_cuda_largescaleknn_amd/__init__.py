@@ -38,8 +38,8 @@ def _hw_queues() -> None:
 
 _hw_queues()
 
-from .models.knn_engine import (KnnConfig, build_index, knn_distances, knn_neighbors,  # noqa: F401
-                                knn_query_distances, knn_query_neighbors, point_radius_counts,
+from .models.knn_engine import (KnnConfig, build_index, cluster_labels, cluster_points,  # noqa: F401
+                                compact_labels, knn_distances, knn_neighbors, knn_query_distances, knn_query_neighbors, point_radius_counts,
                                 point_radius_neighbors, point_radius_query_counts, point_radius_query_neighbors,
                                 point_radius_self_neighbors, prepare_point_radii, query, query_neighbors, query_points,
                                 radius_counts, radius_neighbors, radius_query_counts, radius_query_neighbors,

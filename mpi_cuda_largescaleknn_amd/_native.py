@@ -58,7 +58,7 @@ class TreeView(C.Structure):
     ]
 
 
-HIP_ABI = 12  # lsk_hip_abi_version() of a library matching the structs below
+HIP_ABI = 13  # lsk_hip_abi_version() of a library matching the structs below
 
 
 class KnnArgs(C.Structure):
@@ -140,6 +140,8 @@ def _declare_host(lib: C.CDLL) -> None:
     lib.lsk_cpu_radius_var_count.restype = None
     lib.lsk_cpu_radius_var_fill.argtypes = [vp, i64, vp, i64, vp, vp, vp, vp, vp, i32]
     lib.lsk_cpu_radius_var_fill.restype = None
+    lib.lsk_cpu_cluster.argtypes = [vp, i64, C.c_float, i32, vp, vp, i32]
+    lib.lsk_cpu_cluster.restype = None
     lib.lsk_cpu_count_below.argtypes = [vp, i64, vp, vp, i32, vp, i32]
     lib.lsk_cpu_count_below.restype = None
     lib.lsk_cpu_bounds.argtypes = [vp, i64, vp, i32]
@@ -197,6 +199,9 @@ def _declare_hip(lib: C.CDLL) -> None:
         "lsk_hip_radius_lds_row": ([], i32),
         "lsk_hip_radius_var_count": ([C.POINTER(TreeView), vp, i64, vp, vp, vp, vp, vp, vp], i32),
         "lsk_hip_radius_var_fill": ([C.POINTER(TreeView), vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp], i32),
+        "lsk_hip_cluster_link": ([C.POINTER(TreeView), vp, vp, C.c_float, i32, vp, vp, vp, vp, vp], i32),
+        "lsk_hip_cluster_label": ([C.POINTER(TreeView), vp, vp, vp, i32, vp, vp, vp, vp, vp], i32),
+        "lsk_hip_cluster_border": ([C.POINTER(TreeView), vp, vp, C.c_float, vp, vp, vp, vp, vp], i32),
         "lsk_hip_grid_decide": ([vp, vp, i64, i32, C.c_float, i32, vp, vp], i32),
         "lsk_hip_boundary_groups": ([vp, i32, i64, vp, vp, vp, C.c_int, C.c_int, vp, vp], i32),
         "lsk_hip_grid_build": ([vp, vp, i64, vp, i32, vp, vp], i32),

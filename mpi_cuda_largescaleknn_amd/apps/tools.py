@@ -12,6 +12,9 @@
            (-r R | --radii FILE | --point-radii FILE) [--squared] [--counts-only] [--unsorted]
            -> hipKNN_radius' PREFIX.count (and .offsets / .ids / .dist) for q.float3 against the
               brute-force oracle: every count's consistency with the offsets, sampled rows bitwise
+    python -m mpi_cuda_largescaleknn_amd.apps.tools ccheck in.float3 PREFIX -r EPS [--min-pts M] [--squared]
+           -> hipKNN_cluster's PREFIX.labels and PREFIX.core against the brute-force oracle, every
+              point (at most 65536: the oracle visits every pair)
     python -m mpi_cuda_largescaleknn_amd.apps.tools cat prefix P out.float  (concatenate per-rank outputs)
     python -m mpi_cuda_largescaleknn_amd.apps.tools cmp a.float b.float
 """
@@ -183,6 +186,36 @@ def rcheck(a) -> int:
     return 0 if bad + rows_bad == 0 else 1
 
 
+CCHECK_MAX = 65536  # points ccheck takes: its oracle visits every pair
+
+
+def ccheck(a) -> int:
+    pts = io.read_points(a.inp)
+    n = pts.shape[0]
+    if n > CCHECK_MAX:
+        print(f"ccheck: {n} points, more than {CCHECK_MAX}: the oracle is quadratic (it visits every pair of "
+              "points); check a smaller set")
+        return 1
+    if math.isnan(a.eps) or a.eps < 0 or a.min_pts < 1:
+        print("ccheck: -r must be >= 0 and --min-pts at least 1")
+        return 1
+    labels = io.read_array(a.prefix + ".labels", torch.int32)
+    core = torch.from_numpy(np.fromfile(a.prefix + ".core", dtype=np.uint8))
+    if labels.shape[0] != n or core.shape[0] != n:
+        print(f"size mismatch: {labels.shape[0]} labels, {core.shape[0]} core flags for {n} points")
+        return 1
+    cut2 = float(np.float32(a.eps)) if a.squared else cut2_of(a.eps)
+    ref_l, ref_c = K.cluster_cpu(pts, cut2, a.min_pts)
+    bad_c = (core != ref_c.to(torch.uint8)).nonzero().flatten()
+    bad_l = (labels != ref_l).nonzero().flatten()
+    print(f"checked {n} points: {bad_c.numel()} core flag mismatches, {bad_l.numel()} label mismatches")
+    for i in bad_c[:10].tolist():
+        print(f"CORE {i:012d} = {int(core[i])} (oracle {int(ref_c[i])})")
+    for i in bad_l[:10].tolist():
+        print(f"LABEL {i:012d} = {int(labels[i])} (oracle {int(ref_l[i])})")
+    return 0 if bad_c.numel() + bad_l.numel() == 0 else 1
+
+
 def cat(a) -> int:
     parts = [io.read_floats(f"{a.prefix}_{r:06d}.float") for r in range(a.p)]
     out = torch.cat(parts)
@@ -240,6 +273,12 @@ def main(argv=None) -> int:
     p.add_argument("--samples", type=int, default=1000)
     p.add_argument("--counts-only", action="store_true")
     p.add_argument("--unsorted", action="store_true", help="rows written with --unsorted: compared as sets")
+    p = sub.add_parser("ccheck")
+    p.add_argument("inp")
+    p.add_argument("prefix", help="the -o PREFIX of hipKNN_cluster")
+    p.add_argument("-r", dest="eps", type=float, required=True)
+    p.add_argument("--min-pts", type=int, default=1)
+    p.add_argument("--squared", action="store_true", help="-r is the squared cutoff")
     p = sub.add_parser("cat")
     p.add_argument("prefix")
     p.add_argument("p", type=int)
@@ -249,7 +288,7 @@ def main(argv=None) -> int:
     p.add_argument("a")
     p.add_argument("b")
     a = ap.parse_args(argv)
-    return {"gen": gen, "split": split, "check": check, "rcheck": rcheck, "cat": cat, "cmp": cmp}[a.cmd](a)
+    return {"gen": gen, "split": split, "check": check, "rcheck": rcheck, "ccheck": ccheck, "cat": cat, "cmp": cmp}[a.cmd](a)
 
 
 if __name__ == "__main__":

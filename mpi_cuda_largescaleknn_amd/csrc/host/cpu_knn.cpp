@@ -275,6 +275,59 @@ extern "C" void lsk_cpu_radius_var_fill(const float *pts, int64_t n, const float
   });
 }
 
+// Density clustering by brute force, the definition itself: core[i] = #{ j : dist2 < cut2 } >=
+// min_pts; clusters = connected components of the core points under dist2 < cut2, labelled
+// with their smallest row (the union-find hooks the larger root under the smaller, so a root
+// is its component's smallest row); a non-core point takes the label of its nearest core
+// point by (dist2 bits, row), or -1 (min_pts = 1: its own row) when it has none. The counts
+// and the border points are threaded; the unions run over all pairs in one thread.
+extern "C" void lsk_cpu_cluster(const float *pts, int64_t n, float cut2, int min_pts, int32_t *labels,
+                                uint8_t *core, int nthreads) {
+  const vec3f *P = (const vec3f *)pts;
+  parallel_for(n, nthreads, [&](int64_t b, int64_t e) {
+    for (int64_t i = b; i < e; i++) {
+      int64_t c = 0;
+      for (int64_t j = 0; j < n; j++) c += lsk::dist2(P[i], P[j]) < cut2;
+      core[i] = c >= (int64_t)min_pts;
+    }
+  });
+  std::vector<int32_t> parent((size_t)n);
+  for (int64_t i = 0; i < n; i++) parent[(size_t)i] = (int32_t)i;
+  auto find = [&](int32_t x) {
+    while (parent[(size_t)x] != x) {
+      parent[(size_t)x] = parent[(size_t)parent[(size_t)x]];
+      x = parent[(size_t)x];
+    }
+    return x;
+  };
+  for (int64_t i = 0; i < n; i++) {
+    if (!core[i]) continue;
+    for (int64_t j = i + 1; j < n; j++) {
+      if (!core[j] || !(lsk::dist2(P[i], P[j]) < cut2)) continue;
+      const int32_t a = find((int32_t)i), c = find((int32_t)j);
+      if (a != c) parent[(size_t)std::max(a, c)] = std::min(a, c);
+    }
+  }
+  for (int64_t i = 0; i < n; i++)
+    if (core[i]) labels[i] = find((int32_t)i);
+  // (the roots are final: the border points only read them)
+  parallel_for(n, nthreads, [&](int64_t b, int64_t e) {
+    for (int64_t i = b; i < e; i++) {
+      if (core[i]) continue;
+      uint64_t best = ~0ull;
+      for (int64_t j = 0; j < n; j++) {
+        if (!core[j]) continue;
+        const float v = lsk::dist2(P[i], P[j]);
+        if (v < cut2) best = std::min(best, ((uint64_t)lsk::fbits(v) << 32) | (uint32_t)j);
+      }
+      if (best != ~0ull)
+        labels[i] = labels[(size_t)(uint32_t)best];
+      else
+        labels[i] = min_pts == 1 ? (int32_t)i : -1;
+    }
+  });
+}
+
 extern "C" void lsk_cpu_count_below(const float *pts, int64_t n, const float *qry,
                                     const float *thr, int nq, unsigned long long *counts,
                                     int nthreads) {

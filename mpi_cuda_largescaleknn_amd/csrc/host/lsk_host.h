@@ -98,6 +98,14 @@ void lsk_cpu_radius_var_count(const float *pts, int64_t n, const float *qry, int
 void lsk_cpu_radius_var_fill(const float *pts, int64_t n, const float *qry, int64_t nq, const float *qcut2,
                              const float *pcut2, const int64_t *offsets, int32_t *out_idx, float *out_d2,
                              int nthreads);
+// Density clustering (friends-of-friends / DBSCAN) by brute force over all pairs. core[i] = 1
+// iff #{ j : dist2(p_i, p_j) < cut2 } >= min_pts (strict; the point itself and exact copies
+// count; a point with a NaN or infinite coordinate counts nothing). labels[i]: a core point
+// gets the smallest row among the core points of its connected component (edges: pairs of
+// core points with dist2 < cut2); a non-core point the label of the core point smallest by
+// (dist2 bits, row) among those with dist2 < cut2, and without one -1, or i when min_pts = 1.
+void lsk_cpu_cluster(const float *pts, int64_t n, float cut2, int min_pts, int32_t *labels, uint8_t *core,
+                     int nthreads);
 // Verification counts (= lsk_hip_count_below): counts[2j] += #{p : dist2(q_j,p) < thr[2j]},
 // counts[2j+1] += #{p : dist2(q_j,p) < thr[2j+1]}.
 void lsk_cpu_count_below(const float *pts, int64_t n, const float *qry, const float *thr, int nq,

@@ -1340,3 +1340,101 @@ def point_radius_self_neighbors(points: torch.Tensor, point_radii: torch.Tensor,
     points whose ball contains point i (with the k-th squared distances as squared radii, the
     points that have i among their k nearest, ties at the k-th distance left out)."""
     return point_radius_query_neighbors(points, points, point_radii, squared=squared, sort=sort, max_pairs=max_pairs)
+
+
+# ------------------------------------------------------------------ density clustering
+# the device error word of the last cluster_labels run (tests: always 0)
+LAST_CLUSTER_ERRORS = [0]
+# cluster.hip `half`: a bucket's candidates above a lane's own position are left to their own
+# lanes, so that each pair is united once. On by default: 1e7 uniform points, one giant
+# component, 37.7 against 43.1 ms, near percolation 27.7 against 28.8 ms, no difference where
+# little is linked (scripts/cluster_bench.py --no-half measures the other form)
+CLUSTER_HALF = os.environ.get("LSKNN_CLUSTER_HALF", "1") != "0"
+_CLUSTER_STATS = ("cluster_evals", "cluster_nodes", "cluster_buckets", "cluster_clique_accepts",
+                  "cluster_cas_retries")
+
+
+def _cluster_args(what: str, eps: float, min_pts: int, squared: bool) -> tuple[float, int]:
+    try:
+        cut2 = _radius_cut2(what, eps, squared)
+    except ValueError:
+        raise ValueError(f"{what}: eps must be >= 0 (got {eps})") from None
+    if isinstance(min_pts, bool) or int(min_pts) != min_pts or min_pts < 1:
+        raise ValueError(f"{what}: min_pts must be an integer >= 1 (got {min_pts})")
+    return cut2, int(min_pts)
+
+
+def cluster_labels(index: LocalIndex, eps: float, min_pts: int = 1, squared: bool = False,
+                   stats: KnnStats | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """Density clustering of the points of `index`: (labels int32 [n], core bool [n]) in the
+    order of the indexed array's rows. Friends-of-friends for min_pts = 1, DBSCAN otherwise.
+
+    Two points are linked iff dist2(p, q) < cut2_of(eps) (the strict float32 comparison of
+    radius_counts; squared=True: eps is the squared cutoff itself). A point is a core point
+    iff at least min_pts points, itself and exact copies included, are linked to it
+    (radius_counts of the points against themselves >= min_pts). A cluster is a connected
+    component of the core points under the links, and its label is the smallest row among its
+    core points. A non-core point with a core point within the cutoff takes the label of the
+    one smallest by (dist2 bits, row), the first core entry of its sorted radius_neighbors row;
+    any other non-core point is noise, label -1. With min_pts = 1 there is no noise: a point
+    without any neighbour (eps = 0, or a NaN or infinite coordinate: such a point is linked to
+    nothing, itself included) is not core and forms a cluster of its own, labelled by its row.
+    eps = inf puts all finite points into one cluster. The result depends on the inputs alone,
+    not on the index's internal order or on the order in which the device's unions land.
+
+    No pair is stored: the device links the components with a lock-free union-find while it
+    walks the tree (cluster.hip), so memory is O(n) whatever the density. eps < 0, NaN eps or
+    min_pts < 1 raise ValueError before any kernel runs; an index built in a rotated frame
+    raises too. One host read (the device error word). `stats` receives cluster_evals /
+    _nodes / _buckets / _clique_accepts / _cas_retries and the count pass's radius_* counters."""
+    cut2, min_pts = _cluster_args("cluster_labels", eps, min_pts, squared)
+    if index.qrot is not None:
+        raise ValueError("cluster_labels: an index built in a rotated frame cannot be clustered "
+                         "(build_index(points) without a frame)")
+    n, dev = index.n, index.device
+    if n == 0:
+        return torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.bool, device=dev)
+    if not K.is_gpu(index.pts):
+        KERNELS_USED.add("cpu")
+        return K.cluster_cpu(_input_order(index), cut2, min_pts)
+    raw_r = torch.zeros(4, dtype=torch.int64, device=dev) if stats is not None else None
+    raw_c = torch.zeros(K.CLUSTER_STATS, dtype=torch.int64, device=dev) if stats is not None else None
+    # counts in input order: the sorted points are their own queries, perm their rows
+    counts = K.radius_count_gpu(index.tree(), index.pts, n, cut2, index.perm, stats=raw_r)
+    core = counts >= min_pts
+    core_sorted = core[index.perm[:n].long()].to(torch.uint8)
+    labels, err = K.cluster_gpu(index.tree(), index.perm, core_sorted, cut2, fof=min_pts == 1, border=min_pts > 1,
+                                half=CLUSTER_HALF, stats=raw_c)
+    KERNELS_USED.update(("radius", "cluster"))
+    LAST_CLUSTER_ERRORS[0] = int(err.item()) & 0xFFFFFFFF  # the only host read
+    if LAST_CLUSTER_ERRORS[0]:
+        raise NativeError(f"cluster_labels: {LAST_CLUSTER_ERRORS[0]} parent chains did not end "
+                          "(the union-find's invariant is broken: a bug)")
+    if stats is not None:
+        _add_radius_stats(stats, raw_r)
+        for nm, v in zip(_CLUSTER_STATS, raw_c.cpu().tolist()):
+            stats.counters[nm] = stats.counters.get(nm, 0) + int(v)
+    return labels, core
+
+
+def cluster_points(points: torch.Tensor, eps: float, min_pts: int = 1, squared: bool = False,
+                   stats: KnnStats | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """cluster_labels over an index built once from `points` (float32 [n, 3]), in the points'
+    own frame."""
+    _cluster_args("cluster_points", eps, min_pts, squared)
+    if points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32:
+        raise ValueError("cluster_points: points must be a float32 [n, 3] tensor")
+    if points.shape[0] == 0:  # nothing to index
+        return (torch.empty(0, dtype=torch.int32, device=points.device),
+                torch.empty(0, dtype=torch.bool, device=points.device))
+    return cluster_labels(build_index(points), eps, min_pts, squared=squared, stats=stats)
+
+
+def compact_labels(labels: torch.Tensor) -> tuple[torch.Tensor, int]:
+    """(dense int32 labels, number of clusters): the clusters of cluster_labels numbered 0, 1,
+    ... by ascending label (the smallest row of their core points); -1 stays -1."""
+    noise = labels < 0
+    uniq, inv = torch.unique(labels[~noise], sorted=True, return_inverse=True)
+    dense = torch.full_like(labels, -1, dtype=torch.int32)
+    dense[~noise] = inv.to(torch.int32)
+    return dense, int(uniq.numel())

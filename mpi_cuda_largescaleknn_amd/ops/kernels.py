@@ -828,6 +828,63 @@ def radius_fill_gpu(tree: tuple, perm: torch.Tensor, qsorted: torch.Tensor, nq: 
     return idx, dist, err
 
 
+# --------------------------------------------------------------------------- density clustering
+def cluster_cpu(points: torch.Tensor, cut2: float, min_pts: int = 1) -> tuple[torch.Tensor, torch.Tensor]:
+    """CPU oracle of the density clustering (brute force over all pairs): (labels int32 [n],
+    core bool [n]) in the order of `points`. core: at least min_pts points (itself and exact
+    copies included) with dist2 < cut2 (strict); a core point's label is the smallest row among
+    the core points of its connected component, a non-core point's the label of its nearest
+    core point by (dist2 bits, row) within cut2, else -1 (min_pts = 1: its own row)."""
+    if min_pts < 1 or not cut2 >= 0.0:
+        raise ValueError("cluster_cpu: min_pts must be at least 1 and cut2 >= 0")
+    pts = points.contiguous().float().cpu()
+    n = pts.shape[0]
+    labels = torch.empty(n, dtype=torch.int32)
+    core = torch.empty(n, dtype=torch.uint8)
+    _native.host().lsk_cpu_cluster(_ptr(pts), n, C.c_float(cut2), int(min_pts), _ptr(labels), _ptr(core), _nthreads())
+    return labels, core.bool()
+
+
+CLUSTER_STATS = 5  # cluster.hip: distance evaluations, nodes popped, buckets scanned, clique acceptances, CAS retries
+
+
+def cluster_gpu(tree: tuple, perm: torch.Tensor, core_sorted: torch.Tensor, cut2: float, fof: bool,
+                border: bool, half: bool = False, stats: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """The passes of the density clustering (cluster.hip) on the current stream: (labels int32
+    [n] in input order, err: the device error word, int32 [1]; non-zero: a parent chain did not
+    end, the caller raises). tree: (sorted_pts_padded, nodes, qnodes, n, depth), unrotated, n
+    >= 1; perm: sorted position -> input row; core_sorted: uint8 [n], the core flags at the
+    sorted positions. fof: a non-core point is a cluster of its own (min_pts = 1), else noise;
+    border: also run the border walk (non-core points take their nearest core point's label).
+    half: see lsk_hip_cluster_link. stats: optional zeroed int64 [CLUSTER_STATS]."""
+    pts, nodes, qnodes, n, depth = tree
+    dev = pts.device
+    if not cut2 >= 0.0:
+        raise ValueError("cluster_gpu: cut2 must be >= 0")
+    for t, dt in ((perm, torch.int32), (core_sorted, torch.uint8)):
+        if t.dtype != dt or t.numel() < n or not t.is_contiguous() or t.device != dev:
+            raise ValueError("cluster_gpu: perm int32 [n] and core_sorted uint8 [n], contiguous, on the tree's device")
+    if stats is not None and (stats.dtype != torch.int64 or stats.numel() < CLUSTER_STATS or stats.device != dev):
+        raise ValueError(f"cluster_gpu: stats int64 [{CLUSTER_STATS}] on the tree's device")
+    tv = TreeView(_ptr(pts), _ptr(nodes), _ptr(qnodes), n, depth, 0)
+    cpre = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+    torch.cumsum(core_sorted[:n], 0, dtype=torch.int32, out=cpre[1:])
+    parent = torch.empty(n, dtype=torch.int32, device=dev)
+    root = torch.empty(n, dtype=torch.int32, device=dev)
+    minrow = torch.empty(n, dtype=torch.int32, device=dev)
+    labels = torch.empty(n, dtype=torch.int32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    lib, st = _native.hip(), _stream(pts)
+    check(lib.lsk_hip_cluster_link(C.byref(tv), _ptr(core_sorted), _ptr(cpre), C.c_float(cut2), 1 if half else 0,
+                                   _ptr(parent), _ptr(minrow), _ptr(err), _ptr(stats), st), "cluster_link")
+    check(lib.lsk_hip_cluster_label(C.byref(tv), _ptr(perm), _ptr(core_sorted), _ptr(parent), 1 if fof else 0,
+                                    _ptr(root), _ptr(minrow), _ptr(labels), _ptr(err), st), "cluster_label")
+    if border:
+        check(lib.lsk_hip_cluster_border(C.byref(tv), _ptr(perm), _ptr(core_sorted), C.c_float(cut2), _ptr(root),
+                                         _ptr(minrow), _ptr(labels), _ptr(stats), st), "cluster_border")
+    return labels, err
+
+
 # --------------------------------------------------------------------------- halo
 UB_MAX_W = 8  # tree.hip kUbMaxW: beyond it the box-pair bound
 
