@@ -257,7 +257,7 @@ def build_tree(sorted_pts: torch.Tensor, n: int) -> tuple[torch.Tensor, torch.Te
         ch = nodes[2 * a: 4 * a].view(a, 2, 8)
         nodes[a:2 * a, 0:3] = torch.minimum(ch[:, 0, 0:3], ch[:, 1, 0:3])
         nodes[a:2 * a, 4:7] = torch.maximum(ch[:, 0, 4:7], ch[:, 1, 4:7])
-        nodes[a:2 * a, 3] = torch.maximum(ch[:, 0, 3], ch[:, 1, 3])
+        nodes[a:2 * a, 3] = torch.fmax(ch[:, 0, 3], ch[:, 1, 3])
     return nodes, qnodes, depth
 
 
@@ -270,12 +270,21 @@ def tree_set_radii(nodes: torch.Tensor, n: int, d2_sorted: torch.Tensor) -> torc
     depth = tree_depth(n)
     slots = 1 << depth
     r = torch.zeros(slots * BUCKET, dtype=torch.float32)
-    r[:n] = d2_sorted[:n]
+    d2 = d2_sorted[:n]
+    # an unresolved (NaN) radius widens the bound to +inf, as leaf_radius_kernel does: amax
+    # would keep the NaN, and box_dist2 < NaN then drops every candidate of the subtree
+    r[:n] = torch.where(d2 != d2, torch.full_like(d2, math.inf), d2)
     nodes[slots:, 3] = r.view(slots, BUCKET).amax(dim=1)
+    return _levelup_radii(nodes, depth)
+
+
+def _levelup_radii(nodes: torch.Tensor, depth: int) -> torch.Tensor:
+    """CPU: inner-node radii (lo.w) = max of the children's, up to node 1 (fmaxf as
+    levelup_kernel: a NaN never replaces a number)."""
     for level in range(depth - 1, -1, -1):
         a = 1 << level
         ch = nodes[2 * a: 4 * a].view(a, 2, 8)
-        nodes[a:2 * a, 3] = torch.maximum(ch[:, 0, 3], ch[:, 1, 3])
+        nodes[a:2 * a, 3] = torch.fmax(ch[:, 0, 3], ch[:, 1, 3])
     return nodes
 
 
@@ -928,11 +937,7 @@ def tree_set_radii_ub(nodes: torch.Tensor, pts: torch.Tensor, n: int, k: int) ->
             d2 = torch.addcmul(torch.addcmul(e[:, 0] * e[:, 0], e[:, 1], e[:, 1]), e[:, 2], e[:, 2])
         r[:nb] = d2 * (1.0 + 2.0 ** -16)
     nodes[slots:, 3] = r
-    for level in range(depth - 1, -1, -1):
-        a = 1 << level
-        ch = nodes[2 * a: 4 * a].view(a, 2, 8)
-        nodes[a:2 * a, 3] = torch.maximum(ch[:, 0, 3], ch[:, 1, 3])
-    return nodes
+    return _levelup_radii(nodes, depth)
 
 
 def boundary_groups(local_nodes: torch.Tensor, depth: int, ngroups: int, pub: torch.Tensor, pub_off: list[int],
@@ -1010,6 +1015,8 @@ def halo_mask(pts: torch.Tensor, pub: torch.Tensor, pub_off: list[int], pub_dept
                                               self_rank, _ptr(mask), _stream(pts)), "halo_mask")
         return mask
     # CPU: test against the leaf level of each published tree
+    if nranks > 64:  # one mask bit per rank, as lsk_hip_halo_mask (the host loop stops at 64)
+        raise ValueError("halo_mask: at most 64 ranks")
     boxes, offs = [], [0]
     pub = pub.reshape(-1, 8)
     for j in range(nranks):
