@@ -142,6 +142,12 @@ def _declare_host(lib: C.CDLL) -> None:
     lib.lsk_cpu_radius_var_fill.restype = None
     lib.lsk_cpu_cluster.argtypes = [vp, i64, C.c_float, i32, vp, vp, i32]
     lib.lsk_cpu_cluster.restype = None
+    lib.lsk_cpu_radius_periodic_count.argtypes = [vp, i64, vp, i64, C.c_float, vp, vp, vp, i32]
+    lib.lsk_cpu_radius_periodic_count.restype = None
+    lib.lsk_cpu_radius_periodic_fill.argtypes = [vp, i64, vp, i64, C.c_float, vp, vp, vp, vp, vp, i32]
+    lib.lsk_cpu_radius_periodic_fill.restype = None
+    lib.lsk_cpu_cluster_periodic.argtypes = [vp, i64, C.c_float, i32, vp, vp, vp, i32]
+    lib.lsk_cpu_cluster_periodic.restype = None
     lib.lsk_cpu_count_below.argtypes = [vp, i64, vp, vp, i32, vp, i32]
     lib.lsk_cpu_count_below.restype = None
     lib.lsk_cpu_bounds.argtypes = [vp, i64, vp, i32]
@@ -202,6 +208,12 @@ def _declare_hip(lib: C.CDLL) -> None:
         "lsk_hip_cluster_link": ([C.POINTER(TreeView), vp, vp, C.c_float, i32, vp, vp, vp, vp, vp], i32),
         "lsk_hip_cluster_label": ([C.POINTER(TreeView), vp, vp, vp, i32, vp, vp, vp, vp, vp], i32),
         "lsk_hip_cluster_border": ([C.POINTER(TreeView), vp, vp, C.c_float, vp, vp, vp, vp, vp], i32),
+        "lsk_hip_cluster_init": ([C.POINTER(TreeView), vp, vp, C.c_float, vp, vp, vp], i32),
+        "lsk_hip_radius_periodic_count": ([C.POINTER(TreeView), vp, i64, C.c_float, vp, vp, vp, vp, vp, vp], i32),
+        "lsk_hip_radius_periodic_fill": ([C.POINTER(TreeView), vp, vp, i64, C.c_float, vp, vp, vp, vp, vp, vp, vp,
+                                          vp], i32),
+        "lsk_hip_cluster_periodic_hook": ([C.POINTER(TreeView), vp, vp, C.c_float, vp, i32, vp, vp, vp, vp], i32),
+        "lsk_hip_cluster_periodic_border": ([C.POINTER(TreeView), vp, vp, C.c_float, vp, vp, vp, vp, vp, vp], i32),
         "lsk_hip_grid_decide": ([vp, vp, i64, i32, C.c_float, i32, vp, vp], i32),
         "lsk_hip_boundary_groups": ([vp, i32, i64, vp, vp, vp, C.c_int, C.c_int, vp, vp], i32),
         "lsk_hip_grid_build": ([vp, vp, i64, vp, i32, vp, vp], i32),

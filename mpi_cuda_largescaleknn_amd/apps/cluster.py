@@ -1,7 +1,7 @@
 """hipKNN_cluster — density clustering: friends-of-friends groups and DBSCAN labels.
 
     hipKNN_cluster <points.float3> -r <EPS> [--min-pts M] [--squared] -o <PREFIX>
-                   [--device auto|cuda|cpu] [--stats f.json] [-v]
+                   [--period L | Lx,Ly,Lz] [--device auto|cuda|cpu] [--stats f.json] [-v]
 
 Two points are linked when dist2 < EPS² (float32 product, strict: the comparison of
 hipKNN_radius; --squared: EPS is the squared cutoff itself). A point is a core point when at
@@ -11,6 +11,10 @@ smallest row among its core points. A non-core point takes the label of its near
 point within the cutoff (ties: the lowest row), and is noise (-1) without one; with M = 1 a
 point without any neighbour is a cluster of its own. PREFIX.labels holds one int32 per point
 row, PREFIX.core one byte (1 = core point). Both files are headerless.
+
+--period L or Lx,Ly,Lz (inf: an open axis): the box is periodic and dist2 is that of the
+minimum image of the coordinate difference, so a group across a face is one group; EPS may
+not exceed half the period of a finite axis.
 
 No pair is stored, so memory stays proportional to the number of points however dense the
 set is. One process, one device.
@@ -29,6 +33,7 @@ from ..models import knn_engine as E
 from ..parallel import launch as L
 from ..utils import io
 from .query import _device
+from .radius import add_period_option
 
 
 def parse(argv: list[str]) -> argparse.Namespace:
@@ -38,6 +43,7 @@ def parse(argv: list[str]) -> argparse.Namespace:
     ap.add_argument("--min-pts", type=int, default=1, help="points within EPS that make a core point (default 1)")
     ap.add_argument("--squared", action="store_true", help="EPS is the squared cutoff")
     ap.add_argument("-o", dest="out", required=True, metavar="PREFIX", help="writes PREFIX.labels and PREFIX.core")
+    add_period_option(ap)
     ap.add_argument("--device", choices=["auto", "cuda", "cpu"], default="auto")
     ap.add_argument("--stats", default="", help="write run statistics to this JSON file")
     ap.add_argument("-v", dest="verbose", action="store_true")
@@ -72,7 +78,14 @@ def main(argv: list[str] | None = None) -> int:
     index = E.build_index(points)
     sync()
     t1 = time.perf_counter()
-    labels, core = E.cluster_labels(index, a.eps, a.min_pts, squared=a.squared, stats=stats)
+    try:
+        if a.period is None:
+            labels, core = E.cluster_labels(index, a.eps, a.min_pts, squared=a.squared, stats=stats)
+        else:
+            labels, core = E.cluster_labels(index, a.eps, a.min_pts, squared=a.squared, stats=stats, period=a.period)
+    except ValueError as e:
+        sys.stderr.write(f"hipKNN_cluster: {e}\n")
+        return 1
     labels, core = labels.cpu(), core.cpu()
     t2 = time.perf_counter()
     io.write_array(a.out + ".labels", labels, 0, truncate=True)
@@ -86,6 +99,8 @@ def main(argv: list[str] | None = None) -> int:
         rec = {"n": index.n, "eps": a.eps, "min_pts": a.min_pts, "squared": a.squared, "clusters": nclusters,
                "noise": noise, "largest": largest, "core": int(core.sum()), "device": str(dev),
                "index_s": t1 - t0, "cluster_s": t2 - t1, "kernels": E.kernels_used(), "cluster": stats.counters}
+        if a.period is not None:
+            rec["period"] = list(a.period)
         with open(a.stats, "w") as f:
             json.dump(rec, f, indent=1)
     return 0

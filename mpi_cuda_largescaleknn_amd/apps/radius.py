@@ -2,7 +2,7 @@
 
     hipKNN_radius <points.float3> <queries.float3> (-r <radius> | --radii FILE | --point-radii FILE) [--squared]
                   -o <PREFIX> [--counts-only] [--unsorted] [--chunk N] [--max-pairs M]
-                  [--device auto|cuda|cpu] [--stats f.json] [-v]
+                  [--period L | Lx,Ly,Lz] [--device auto|cuda|cpu] [--stats f.json] [-v]
 
 For every row of the query file, the points of the point file with dist2 < radius² (float32
 product, strict: the comparison of the -r cutoff of the k-NN tools), however many there
@@ -13,6 +13,10 @@ point row (scatter: dist2 < the point's radius², the points whose own ball hold
 in CSR form: PREFIX.offsets (int64 [nq + 1], row q = [offsets[q], offsets[q + 1])),
 PREFIX.ids (int32 [total], rows of the point file) and PREFIX.dist (float32 [total]); each
 row ascending by (distance, row) unless --unsorted. All files are headerless.
+
+--period L or Lx,Ly,Lz (inf: an open axis): the box is periodic, distances are those of the
+minimum image of the coordinate difference (lsknn_tools wrap brings coordinates into one
+period); a radius may not exceed half the period of a finite axis. Not with --point-radii.
 
 The index over the points is built once; the queries go through it in chunks of --chunk
 rows. A chunk with more than --max-pairs pairs is split along its counts' prefix sums into
@@ -30,13 +34,30 @@ import time
 import torch
 
 from ..models import knn_engine as E
+from ..ops import kernels as K
 from ..parallel import launch as L
 from ..utils import io
 from .query import _device
 
 
+def period_arg(text: str) -> tuple[float, float, float]:
+    """--period L | Lx,Ly,Lz: three values > 0, inf = open axis (also hipKNN_cluster, lsknn_tools)."""
+    try:
+        vals = [float(v) for v in text.split(",")]
+        if len(vals) == 1:
+            vals = vals * 3
+        return K.check_period("--period", vals)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
+def add_period_option(ap: argparse.ArgumentParser) -> None:
+    ap.add_argument("--period", type=period_arg, default=None, metavar="L | Lx,Ly,Lz",
+                    help="periodic box: minimum-image distances (inf: an open axis)")
+
+
 def add_radius_options(ap: argparse.ArgumentParser) -> None:
-    """Exactly one of -r / --radii / --point-radii, and --squared (also lsknn_tools rcheck)."""
+    """Exactly one of -r / --radii / --point-radii, --squared and --period (also lsknn_tools rcheck)."""
     g = ap.add_mutually_exclusive_group(required=True)
     g.add_argument("-r", dest="radius", type=float, default=None, help="one radius for every query")
     g.add_argument("--radii", default=None, metavar="FILE",
@@ -44,6 +65,7 @@ def add_radius_options(ap: argparse.ArgumentParser) -> None:
     g.add_argument("--point-radii", default=None, metavar="FILE",
                    help="headerless float32 file, one radius per point row: points whose own ball holds the query")
     ap.add_argument("--squared", action="store_true", help="the given values are squared cutoffs")
+    add_period_option(ap)
 
 
 def read_radii(path: str, what: str, rows: int, of: str) -> torch.Tensor:
@@ -99,6 +121,17 @@ def main(argv: list[str] | None = None) -> int:
         sys.stderr.write("hipKNN_radius: runs as one process on one device (radius queries over several ranks "
                          "are not supported)\n")
         return 1
+    if a.period is not None and a.point_radii is not None:
+        sys.stderr.write("hipKNN_radius: --period is not supported with --point-radii\n")
+        return 1
+    try:
+        if a.period is not None and a.radius is not None:
+            E.check_period_radius("-r", a.radius, a.squared, a.period)
+    except ValueError as e:
+        sys.stderr.write(f"hipKNN_radius: {e}\n")
+        return 1
+    # (None: the calls below are the ones without the keyword)
+    per = {} if a.period is None else {"period": a.period}
     dev = _device(a.device)
     gpu = dev.type == "cuda"
     stats = E.KnnStats() if a.stats else None
@@ -118,11 +151,11 @@ def main(argv: list[str] | None = None) -> int:
                 raise ValueError(f"--radii {a.radii}: every value must be >= 0 and not NaN")
 
             def count_fn(q, b, e):
-                return E.radius_counts(index, q, qrad[b:e].to(dev), stats=stats, squared=a.squared)
+                return E.radius_counts(index, q, qrad[b:e].to(dev), stats=stats, squared=a.squared, **per)
 
             def lists_fn(q, b, e):
                 return E.radius_neighbors(index, q, qrad[b:e].to(dev), sort=not a.unsorted, max_pairs=a.max_pairs,
-                                          squared=a.squared)
+                                          squared=a.squared, **per)
         elif a.point_radii is not None:
             prad = E.prepare_point_radii(index, read_radii(a.point_radii, "--point-radii", index.n, a.points).to(dev),
                                          squared=a.squared)
@@ -134,11 +167,11 @@ def main(argv: list[str] | None = None) -> int:
                 return E.point_radius_neighbors(index, q, prad, sort=not a.unsorted, max_pairs=a.max_pairs)
         else:
             def count_fn(q, b, e):
-                return E.radius_counts(index, q, a.radius, stats=stats, squared=a.squared)
+                return E.radius_counts(index, q, a.radius, stats=stats, squared=a.squared, **per)
 
             def lists_fn(q, b, e):
                 return E.radius_neighbors(index, q, a.radius, sort=not a.unsorted, max_pairs=a.max_pairs,
-                                          squared=a.squared)
+                                          squared=a.squared, **per)
     except ValueError as e:
         sys.stderr.write(f"hipKNN_radius: {e}\n")
         return 1
@@ -151,7 +184,13 @@ def main(argv: list[str] | None = None) -> int:
     pairs = 0  # pairs written so far = the global offset of the next row
     for begin in range(0, nq, a.chunk):
         q = io.read_range(a.queries, begin, min(a.chunk, nq - begin), pin_memory=gpu).to(dev)
-        counts = count_fn(q, begin, begin + q.shape[0]).cpu()
+        try:
+            counts = count_fn(q, begin, begin + q.shape[0]).cpu()
+        except ValueError as e:  # (a --radii entry above half the period)
+            if a.period is None:
+                raise
+            sys.stderr.write(f"hipKNN_radius: {e}\n")
+            return 1
         io.write_array(a.out + ".count", counts, begin, truncate=False)
         if not lists:
             pairs += int(counts.sum())
@@ -184,6 +223,8 @@ def main(argv: list[str] | None = None) -> int:
             rec.update({"radii": a.radii, "point_radii": a.point_radii})
         if a.squared:
             rec["squared"] = True
+        if a.period is not None:
+            rec["period"] = list(a.period)
         with open(a.stats, "w") as f:
             json.dump(rec, f, indent=1)
     return 0

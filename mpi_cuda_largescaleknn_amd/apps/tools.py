@@ -10,11 +10,15 @@
               disabled '#if 0' RES dump, unorderedDataVariant.cu:215-227)
     python -m mpi_cuda_largescaleknn_amd.apps.tools rcheck in.float3 q.float3 PREFIX [--samples S]
            (-r R | --radii FILE | --point-radii FILE) [--squared] [--counts-only] [--unsorted]
+           [--period L | Lx,Ly,Lz]
            -> hipKNN_radius' PREFIX.count (and .offsets / .ids / .dist) for q.float3 against the
               brute-force oracle: every count's consistency with the offsets, sampled rows bitwise
     python -m mpi_cuda_largescaleknn_amd.apps.tools ccheck in.float3 PREFIX -r EPS [--min-pts M] [--squared]
+           [--period L | Lx,Ly,Lz]
            -> hipKNN_cluster's PREFIX.labels and PREFIX.core against the brute-force oracle, every
               point (at most 65536: the oracle visits every pair)
+    python -m mpi_cuda_largescaleknn_amd.apps.tools wrap in.float3 out.float3 --period L | Lx,Ly,Lz [--origin O | Ox,Oy,Oz]
+           -> the points brought into one period [O, O + L) per finite axis (knn_engine.wrap_points)
     python -m mpi_cuda_largescaleknn_amd.apps.tools cat prefix P out.float  (concatenate per-rank outputs)
     python -m mpi_cuda_largescaleknn_amd.apps.tools cmp a.float b.float
 """
@@ -27,7 +31,7 @@ import sys
 import numpy as np
 import torch
 
-from ..models.knn_engine import cut2_of
+from ..models.knn_engine import cut2_of, wrap_points
 from ..ops import kernels as K
 from ..utils import io
 
@@ -119,11 +123,17 @@ def rcheck(a) -> int:
     pts = io.read_points(a.inp)
     qry = io.read_points(a.queries)
     nq = qry.shape[0]
+    if a.period is not None and a.point_radii is not None:
+        print("rcheck: --period is not supported with --point-radii")
+        return 1
     # the oracle of the sampled queries idx: (counts, lists) under the option given
     if a.radius is not None:
         cut2 = float(np.float32(a.radius)) if a.squared else cut2_of(a.radius)
 
         def oracle(idx):
+            if a.period is not None:
+                return (K.radius_periodic_count_cpu(pts, qry[idx], cut2, a.period),
+                        lambda: K.radius_periodic_cpu(pts, qry[idx], cut2, a.period))
             return K.radius_count_cpu(pts, qry[idx], cut2), lambda: K.radius_cpu(pts, qry[idx], cut2)
     else:
         from .radius import read_radii
@@ -139,6 +149,9 @@ def rcheck(a) -> int:
 
         def oracle(idx):
             qc, pc = (c2[idx], None) if a.radii is not None else (None, c2)
+            if a.period is not None:
+                return (K.radius_periodic_count_cpu(pts, qry[idx], 0.0, a.period, qc),
+                        lambda: K.radius_periodic_cpu(pts, qry[idx], 0.0, a.period, qc))
             return K.radius_var_count_cpu(pts, qry[idx], qc, pc), lambda: K.radius_var_cpu(pts, qry[idx], qc, pc)
     counts = io.read_array(a.prefix + ".count", torch.int32)
     if counts.shape[0] != nq:
@@ -205,7 +218,10 @@ def ccheck(a) -> int:
         print(f"size mismatch: {labels.shape[0]} labels, {core.shape[0]} core flags for {n} points")
         return 1
     cut2 = float(np.float32(a.eps)) if a.squared else cut2_of(a.eps)
-    ref_l, ref_c = K.cluster_cpu(pts, cut2, a.min_pts)
+    if a.period is not None:
+        ref_l, ref_c = K.cluster_periodic_cpu(pts, cut2, a.min_pts, a.period)
+    else:
+        ref_l, ref_c = K.cluster_cpu(pts, cut2, a.min_pts)
     bad_c = (core != ref_c.to(torch.uint8)).nonzero().flatten()
     bad_l = (labels != ref_l).nonzero().flatten()
     print(f"checked {n} points: {bad_c.numel()} core flag mismatches, {bad_l.numel()} label mismatches")
@@ -214,6 +230,19 @@ def ccheck(a) -> int:
     for i in bad_l[:10].tolist():
         print(f"LABEL {i:012d} = {int(labels[i])} (oracle {int(ref_l[i])})")
     return 0 if bad_c.numel() + bad_l.numel() == 0 else 1
+
+
+def wrap(a) -> int:
+    pts = io.read_points(a.inp)
+    try:
+        origin = [float(v) for v in a.origin.split(",")]
+        out = wrap_points(pts, a.period, origin[0] if len(origin) == 1 else origin)
+    except ValueError as e:
+        print(f"wrap: {e}")
+        return 1
+    io.write_points(a.out, out)
+    print(f"wrote {out.shape[0]} points to {a.out}")
+    return 0
 
 
 def cat(a) -> int:
@@ -268,7 +297,7 @@ def main(argv=None) -> int:
     p.add_argument("inp")
     p.add_argument("queries")
     p.add_argument("prefix", help="the -o PREFIX of hipKNN_radius")
-    from .radius import add_radius_options
+    from .radius import add_period_option, add_radius_options
     add_radius_options(p)
     p.add_argument("--samples", type=int, default=1000)
     p.add_argument("--counts-only", action="store_true")
@@ -279,6 +308,12 @@ def main(argv=None) -> int:
     p.add_argument("-r", dest="eps", type=float, required=True)
     p.add_argument("--min-pts", type=int, default=1)
     p.add_argument("--squared", action="store_true", help="-r is the squared cutoff")
+    add_period_option(p)
+    p = sub.add_parser("wrap")
+    p.add_argument("inp")
+    p.add_argument("out")
+    add_period_option(p)
+    p.add_argument("--origin", default="0", metavar="O | Ox,Oy,Oz", help="lower corner of the period (default 0)")
     p = sub.add_parser("cat")
     p.add_argument("prefix")
     p.add_argument("p", type=int)
@@ -288,7 +323,10 @@ def main(argv=None) -> int:
     p.add_argument("a")
     p.add_argument("b")
     a = ap.parse_args(argv)
-    return {"gen": gen, "split": split, "check": check, "rcheck": rcheck, "ccheck": ccheck, "cat": cat, "cmp": cmp}[a.cmd](a)
+    if a.cmd == "wrap" and a.period is None:
+        ap.error("wrap: --period is required")
+    return {"gen": gen, "split": split, "check": check, "rcheck": rcheck, "ccheck": ccheck, "wrap": wrap, "cat": cat,
+            "cmp": cmp}[a.cmd](a)
 
 
 if __name__ == "__main__":

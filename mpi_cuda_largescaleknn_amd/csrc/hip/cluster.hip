@@ -55,12 +55,19 @@
 //    workgroups. A chain of parents strictly decreases, so a find ends within n steps; one
 //    that does not bumps the error word and gives up (the host raises: a bug, no fallback).
 // The components do not depend on the order in which the hooks land; the labels are taken
-// from the components alone (smallest input row), so neither do they.
-#include "ball_walk.h"
+// from the components alone (smallest input row), so neither do they. unite, find and the
+// node helpers live in cluster_uf.h, shared with the periodic walks of periodic.hip.
+#include "cluster_uf.h"
 
 namespace {
 
+using lsk::add_stats;
+using lsk::all_core;
 using lsk::fbits;
+using lsk::load_own;
+using lsk::node_span;
+using lsk::tight;
+using lsk::unite;
 
 constexpr int kWaves = 4;  // waves per block, one bucket each (as radius.hip)
 
@@ -81,67 +88,6 @@ struct ClusterArgs {
   unsigned long long *stats; // optional [5]: distance evaluations, nodes popped, buckets
                              // scanned, clique acceptances, CAS retries
 };
-
-// Sorted positions [p0, p1) of `node` at level lvl (its buckets, the last one clipped at n).
-__device__ __forceinline__ void node_span(const lsk_tree_view &T, uint32_t node, int32_t lvl, int64_t &p0,
-                                          int64_t &p1) {
-  const int32_t span_lg = T.depth - lvl;
-  const int64_t first = ((int64_t)node - ((int64_t)1 << lvl)) << span_lg;
-  p0 = first * lsk::kBucket;
-  p1 = min(T.n, (first + ((int64_t)1 << span_lg)) * lsk::kBucket);
-}
-
-__device__ __forceinline__ bool tight(const float4 &lo4, const float4 &hi4, float cut2) {
-  return lsk::dist2(hi4.x - lo4.x, hi4.y - lo4.y, hi4.z - lo4.z) < cut2;
-}
-
-__device__ __forceinline__ bool all_core(const int32_t *cpre, int64_t p0, int64_t p1) {
-  return p1 > p0 && (int64_t)(cpre[p1] - cpre[p0]) == p1 - p0;
-}
-
-__device__ __forceinline__ uint32_t hint(const uint32_t *p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// A root of x's component as far as the hints tell, with path halving (atomicMin: parent[x]
-// only ever decreases, and only for an x that is no root).
-__device__ __forceinline__ uint32_t find(uint32_t *parent, uint32_t x, uint32_t n, bool &bad) {
-  for (uint32_t steps = 0;; steps++) {
-    const uint32_t p = hint(parent + x);
-    if (p == x) return x;
-    if (p > x || steps > n) {  // (never: a parent lies below its child, so a chain ends within n steps)
-      bad = true;
-      return x;
-    }
-    const uint32_t g = hint(parent + p);
-    if (g == p) return p;
-    if (g > p) {
-      bad = true;
-      return x;
-    }
-    atomicMin(parent + x, g);
-    x = g;
-  }
-}
-
-// Links the components of the lane's own point (rq: a position of it, kept as low as the lane
-// has seen) and of b.
-__device__ __forceinline__ void unite(uint32_t *parent, uint32_t &rq, uint32_t b, uint32_t n, bool &bad,
-                                      uint32_t &retries) {
-  uint32_t ra = find(parent, rq, n, bad), rb = find(parent, b, n, bad);
-  while (ra != rb && !bad) {
-    const uint32_t hi = max(ra, rb), lo = min(ra, rb);
-    const uint32_t old = atomicCAS(parent + hi, hi, lo);
-    if (old == hi) {  // hooked
-      ra = rb = lo;
-      break;
-    }
-    retries++;  // hi was hooked meanwhile: old < hi is its parent
-    ra = find(parent, old, n, bad);
-    rb = lo;
-  }
-  rq = min(ra, rb);
-}
 
 __global__ __launch_bounds__(kWaves * 64) void cluster_init_kernel(const ClusterArgs A) {
   const int lane = lsk::lane_id();
@@ -201,33 +147,6 @@ __device__ __forceinline__ int scan_bucket_core(const lsk_tree_view &T, const ui
     if (use) cand(lsk::dist2(Q.x - x, Q.y - y, Q.z - z), c, (uint32_t)(base + j), id, use);
   }
   return cnt;
-}
-
-// The lane's point of bucket g: a GroupQuery whose row is the sorted position itself.
-__device__ __forceinline__ lsk::GroupQuery load_own(const lsk_tree_view &T, int64_t g, int lane) {
-  lsk::GroupQuery Q{g * lsk::kBucket + lane, 0, 0.f, 0.f, 0.f, false, false};
-  Q.valid = Q.qi < T.n;
-  if (Q.valid) {
-    Q.x = T.pts[3 * Q.qi];
-    Q.y = T.pts[3 * Q.qi + 1];
-    Q.z = T.pts[3 * Q.qi + 2];
-    Q.row = Q.qi;
-  }
-  Q.finite = Q.valid && lsk::finite3(Q.x, Q.y, Q.z);
-  return Q;
-}
-
-__device__ __forceinline__ void add_stats(unsigned long long *stats, int lane, uint32_t evals, uint32_t nodes,
-                                          uint32_t buckets, uint32_t accepts, uint32_t retries) {
-  if (!stats) return;
-  const uint32_t e = lsk::wave_sum(evals), a = lsk::wave_sum(accepts), r = lsk::wave_sum(retries);
-  if (lane == 0) {
-    atomicAdd(&stats[0], (unsigned long long)e);
-    atomicAdd(&stats[1], (unsigned long long)nodes);
-    atomicAdd(&stats[2], (unsigned long long)buckets);
-    atomicAdd(&stats[3], (unsigned long long)a);
-    atomicAdd(&stats[4], (unsigned long long)r);
-  }
 }
 
 __global__ __launch_bounds__(kWaves * 64) void cluster_hook_kernel(const ClusterArgs A) {
@@ -460,6 +379,24 @@ extern "C" int lsk_hip_cluster_link(const lsk_tree_view *tree, const uint8_t *co
   LSK_CHECK_LAUNCH("cluster init");
   cluster_hook_kernel<<<blocks, kWaves * 64, 0, (hipStream_t)stream>>>(A);
   LSK_CHECK_LAUNCH("cluster hook");
+  return 0;
+}
+
+// The init pass of lsk_hip_cluster_link alone: the periodic hook (periodic.hip) runs after it.
+extern "C" int lsk_hip_cluster_init(const lsk_tree_view *tree, const uint8_t *core, const int32_t *cpre, float cut2,
+                                    uint32_t *parent, uint32_t *minrow, void *stream) {
+  ClusterArgs A;
+  if (cluster_args("cluster_init", tree, core, cut2, &A)) return 1;
+  if (!cpre || !parent || !minrow) {
+    lsk::set_last_error("cluster_init: null argument");
+    return 1;
+  }
+  A.cpre = cpre;
+  A.parent = parent;
+  A.minrow = minrow;
+  const unsigned blocks = lsk_blocks((A.T.n + lsk::kBucket - 1) / lsk::kBucket, kWaves);
+  cluster_init_kernel<<<blocks, kWaves * 64, 0, (hipStream_t)stream>>>(A);
+  LSK_CHECK_LAUNCH("cluster init");
   return 0;
 }
 

@@ -328,6 +328,116 @@ extern "C" void lsk_cpu_cluster(const float *pts, int64_t n, float cut2, int min
   });
 }
 
+// ---- periodic box: the minimum image of the difference, written out literally ----------------
+// Per axis d = q - p; h = 0.5f * L; d > h: d - L; d < -h: d + L (L = inf never wraps); then the
+// canonical dist2. Symmetric in its bits (fl(q - p) = -fl(p - q), mirrored branches).
+namespace {
+
+inline float wrap_diff(float d, float L) {
+  const float h = 0.5f * L;
+  if (d > h)
+    d = d - L;
+  else if (d < -h)
+    d = d + L;
+  return d;
+}
+
+inline float pdist2(const vec3f &q, const vec3f &p, const float *L) {
+  return lsk::dist2(wrap_diff(q.x - p.x, L[0]), wrap_diff(q.y - p.y, L[1]), wrap_diff(q.z - p.z, L[2]));
+}
+
+}  // namespace
+
+// lsk_cpu_radius_count under a period; qcut2 (optional, [nq]) replaces cut2 per query.
+extern "C" void lsk_cpu_radius_periodic_count(const float *pts, int64_t n, const float *qry, int64_t nq, float cut2,
+                                              const float *qcut2, const float *period, int32_t *counts,
+                                              int nthreads) {
+  const vec3f *P = (const vec3f *)pts;
+  const vec3f *Q = (const vec3f *)qry;
+  parallel_for(nq, nthreads, [&](int64_t b, int64_t e) {
+    for (int64_t qi = b; qi < e; qi++) {
+      const float c2 = qcut2 ? qcut2[qi] : cut2;
+      int32_t c = 0;
+      for (int64_t i = 0; i < n; i++) c += pdist2(Q[qi], P[i], period) < c2;
+      counts[qi] = c;
+    }
+  });
+}
+
+// lsk_cpu_radius_fill under a period, the same CSR form and row order.
+extern "C" void lsk_cpu_radius_periodic_fill(const float *pts, int64_t n, const float *qry, int64_t nq, float cut2,
+                                             const float *qcut2, const float *period, const int64_t *offsets,
+                                             int32_t *out_idx, float *out_d2, int nthreads) {
+  const vec3f *P = (const vec3f *)pts;
+  const vec3f *Q = (const vec3f *)qry;
+  parallel_for(nq, nthreads, [&](int64_t b, int64_t e) {
+    std::vector<uint64_t> d;  // d2 bits << 32 | input row, as lsk_cpu_knn_brute
+    for (int64_t qi = b; qi < e; qi++) {
+      const float c2 = qcut2 ? qcut2[qi] : cut2;
+      d.clear();
+      for (int64_t i = 0; i < n; i++) {
+        const float v = pdist2(Q[qi], P[i], period);
+        if (v < c2) d.push_back(((uint64_t)lsk::fbits(v) << 32) | (uint32_t)i);
+      }
+      std::sort(d.begin(), d.end());
+      // (offsets come from lsk_cpu_radius_periodic_count with the same cutoffs)
+      const size_t m = std::min<size_t>(d.size(), (size_t)(offsets[qi + 1] - offsets[qi]));
+      for (size_t j = 0; j < m; j++) {
+        out_idx[offsets[qi] + (int64_t)j] = (int32_t)(uint32_t)d[j];
+        out_d2[offsets[qi] + (int64_t)j] = lsk::bitsf((uint32_t)(d[j] >> 32));
+      }
+    }
+  });
+}
+
+// lsk_cpu_cluster under a period: the same definition with pdist2 for dist2.
+extern "C" void lsk_cpu_cluster_periodic(const float *pts, int64_t n, float cut2, int min_pts, const float *period,
+                                         int32_t *labels, uint8_t *core, int nthreads) {
+  const vec3f *P = (const vec3f *)pts;
+  parallel_for(n, nthreads, [&](int64_t b, int64_t e) {
+    for (int64_t i = b; i < e; i++) {
+      int64_t c = 0;
+      for (int64_t j = 0; j < n; j++) c += pdist2(P[i], P[j], period) < cut2;
+      core[i] = c >= (int64_t)min_pts;
+    }
+  });
+  std::vector<int32_t> parent((size_t)n);
+  for (int64_t i = 0; i < n; i++) parent[(size_t)i] = (int32_t)i;
+  auto find = [&](int32_t x) {
+    while (parent[(size_t)x] != x) {
+      parent[(size_t)x] = parent[(size_t)parent[(size_t)x]];
+      x = parent[(size_t)x];
+    }
+    return x;
+  };
+  for (int64_t i = 0; i < n; i++) {
+    if (!core[i]) continue;
+    for (int64_t j = i + 1; j < n; j++) {
+      if (!core[j] || !(pdist2(P[i], P[j], period) < cut2)) continue;
+      const int32_t a = find((int32_t)i), c = find((int32_t)j);
+      if (a != c) parent[(size_t)std::max(a, c)] = std::min(a, c);
+    }
+  }
+  for (int64_t i = 0; i < n; i++)
+    if (core[i]) labels[i] = find((int32_t)i);
+  // (the roots are final: the border points only read them)
+  parallel_for(n, nthreads, [&](int64_t b, int64_t e) {
+    for (int64_t i = b; i < e; i++) {
+      if (core[i]) continue;
+      uint64_t best = ~0ull;
+      for (int64_t j = 0; j < n; j++) {
+        if (!core[j]) continue;
+        const float v = pdist2(P[i], P[j], period);
+        if (v < cut2) best = std::min(best, ((uint64_t)lsk::fbits(v) << 32) | (uint32_t)j);
+      }
+      if (best != ~0ull)
+        labels[i] = labels[(size_t)(uint32_t)best];
+      else
+        labels[i] = min_pts == 1 ? (int32_t)i : -1;
+    }
+  });
+}
+
 extern "C" void lsk_cpu_count_below(const float *pts, int64_t n, const float *qry,
                                     const float *thr, int nq, unsigned long long *counts,
                                     int nthreads) {

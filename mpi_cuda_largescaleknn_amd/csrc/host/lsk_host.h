@@ -106,7 +106,18 @@ void lsk_cpu_radius_var_fill(const float *pts, int64_t n, const float *qry, int6
 // (dist2 bits, row) among those with dist2 < cut2, and without one -1, or i when min_pts = 1.
 void lsk_cpu_cluster(const float *pts, int64_t n, float cut2, int min_pts, int32_t *labels, uint8_t *core,
                      int nthreads);
-// Verification counts (= lsk_hip_count_below): counts[2j] += #{p : dist2(q_j,p) < thr[2j]},
+// The three above under a period (three values > 0, +inf = open axis): dist2 is replaced by the
+// minimum image of the difference — per axis d = q - p, h = 0.5f * L, d > h: d - L, d < -h:
+// d + L, in float32 and in this order — then the canonical dist2. qcut2 (optional, [nq])
+// replaces cut2 per query.
+void lsk_cpu_radius_periodic_count(const float *pts, int64_t n, const float *qry, int64_t nq, float cut2,
+                                   const float *qcut2, const float *period, int32_t *counts, int nthreads);
+void lsk_cpu_radius_periodic_fill(const float *pts, int64_t n, const float *qry, int64_t nq, float cut2,
+                                  const float *qcut2, const float *period, const int64_t *offsets,
+                                  int32_t *out_idx, float *out_d2, int nthreads);
+void lsk_cpu_cluster_periodic(const float *pts, int64_t n, float cut2, int min_pts, const float *period,
+                              int32_t *labels, uint8_t *core, int nthreads);
+// Verification counts (= lsk_hip_count_below): counts[2j] +=#{p : dist2(q_j,p) < thr[2j]},
 // counts[2j+1] += #{p : dist2(q_j,p) < thr[2j+1]}.
 void lsk_cpu_count_below(const float *pts, int64_t n, const float *qry, const float *thr, int nq,
                          unsigned long long *counts, int nthreads);

@@ -1061,10 +1061,11 @@ def _empty_csr(nq: int, dev: torch.device) -> tuple:
 
 # ---- variable radii: one per query (gather) or one per indexed point (scatter)
 def _cut2_tensor(what: str, name: str, radii: torch.Tensor, count: int, device: torch.device,
-                 squared: bool) -> torch.Tensor:
+                 squared: bool, upper: float | None = None) -> torch.Tensor:
     """The float32 [count] squared cutoffs of a radius tensor (`squared`: the tensor itself).
     Wrong type, shape or device, or an entry that is negative or NaN: ValueError (one small
-    device reduction is read for the last)."""
+    device reduction is read for the last). upper: the largest entry a period admits; an entry
+    above it raises too, in the same reduction."""
     if not isinstance(radii, torch.Tensor) or radii.dtype != torch.float32 or radii.dim() != 1 \
             or radii.shape[0] != count:
         got = f"{radii.dtype} {tuple(radii.shape)}" if isinstance(radii, torch.Tensor) else type(radii).__name__
@@ -1072,7 +1073,11 @@ def _cut2_tensor(what: str, name: str, radii: torch.Tensor, count: int, device: 
     if radii.device != device:
         raise ValueError(f"{what}: {name} on {radii.device}, the index on {device}")
     r = radii.contiguous()
-    if count and not bool((r >= 0).all()):  # (a NaN fails the comparison too)
+    if upper is not None:
+        if count and not bool(((r >= 0) & (r <= upper)).all()):
+            raise ValueError(f"{what}: every entry of {name} must be >= 0, not NaN and at most half the "
+                             f"period of every finite axis ({upper} here)")
+    elif count and not bool((r >= 0).all()):  # (a NaN fails the comparison too)
         raise ValueError(f"{what}: every entry of {name} must be >= 0 and not NaN")
     return r if squared else r * r
 
@@ -1171,8 +1176,124 @@ def _var_neighbors(what: str, index: LocalIndex, queries: torch.Tensor, qcut2: t
     return offsets, idx, dist
 
 
+# ---- periodic box: the minimum image of the difference (periodic.hip)
+def wrap_points(points: torch.Tensor, period, origin=0.0) -> torch.Tensor:
+    """`points` (float32 [n, 3]) brought into one period: on every finite axis the result lies in
+    [origin, origin + L), also after rounding, and wrapping it again changes nothing; open axes
+    (L = inf) and NaN or infinite coordinates pass through. period / origin: one value or three.
+    The periodic searches take any finite input (a single wrap per axis, literally); for
+    coordinates inside one period their distance is the physical periodic one."""
+    per = K.check_period("wrap_points", period)
+    if points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32:
+        raise ValueError("wrap_points: points must be a float32 [n, 3] tensor")
+    org = (origin,) * 3 if isinstance(origin, (int, float)) else tuple(origin)
+    if len(org) != 3 or not all(math.isfinite(float(o)) for o in org):
+        raise ValueError("wrap_points: origin must be one finite value or three")
+    out = points.clone()
+    for a in range(3):
+        if not math.isfinite(per[a]):
+            continue
+        L, o = float(per[a]), float(np.float32(org[a]))
+        hi = float(np.float32(o) + np.float32(L))  # fl(origin + L): the first value no longer inside
+        x = out[:, a]
+        # float64 holds x - origin and the multiple of L without a visible error; what rounding to
+        # float32 (or the floor's own last bit) leaves on or past an edge is the lower edge itself
+        y = x.double()
+        w = (y - torch.floor((y - o) / L) * L).float()
+        w = torch.where((w >= hi) | (w < o), torch.full_like(w, o), w)
+        out[:, a] = torch.where(torch.isfinite(x), w, x)
+    return out
+
+
+def period_radius_bound(per: tuple, squared: bool) -> float:
+    """The largest radius (squared: squared cutoff) the period `per` admits: fl(0.5 L) (squared:
+    fl(h h)) of its shortest finite axis, inf when every axis is open."""
+    finite = [np.float32(0.5) * np.float32(v) for v in per if math.isfinite(v)]
+    if not finite:
+        return math.inf
+    return K.period_cut2_bound(per) if squared else float(min(finite))
+
+
+def check_period_radius(what: str, radius: float, squared: bool, period, name: str = "radius") -> tuple:
+    """The checked period values of a search with one radius; ValueError for a bad period or a
+    radius above period_radius_bound."""
+    per = K.check_period(what, period)
+    upper = period_radius_bound(per, squared)
+    if float(np.float32(radius)) > upper:
+        raise ValueError(f"{what}: {name} {radius} exceeds half the period of a finite axis "
+                         f"({'squared ' if squared else ''}bound {upper})")
+    return per
+
+
+def _period_cutoffs(what: str, index: LocalIndex, queries: torch.Tensor, radius, squared: bool, period) -> tuple:
+    """The checked arguments of a periodic radius search: (period values, queries, cut2, qcut2).
+    The radius, one value or one per query, may not exceed half the period of a finite axis (r
+    <= fl(0.5 L); squared: cut2 <= fl(h h)): ValueError before any kernel runs, for a tensor in
+    the one reduction that checks its entries."""
+    per = K.check_period(what, period)
+    queries = _check_foreign(what, index, queries)
+    if isinstance(radius, torch.Tensor):
+        upper = period_radius_bound(per, squared)
+        qcut2 = _cut2_tensor(what, "radius", radius, queries.shape[0], index.device, squared,
+                             upper=None if math.isinf(upper) else upper)
+        return per, queries, 0.0, qcut2
+    cut2 = _radius_cut2(what, radius, squared)
+    check_period_radius(what, radius, squared, per)
+    return per, queries, cut2, None
+
+
+_RADIUS_PERIODIC_STATS = _RADIUS_STATS + ("radius_images",)
+
+
+def _periodic_counts(index: LocalIndex, queries: torch.Tensor, cut2: float, qcut2: torch.Tensor | None,
+                     per: tuple, stats: KnnStats | None, _sorted: tuple | None = None) -> torch.Tensor:
+    nq, n = queries.shape[0], index.n
+    if nq == 0 or n == 0:
+        return torch.zeros(nq, dtype=torch.int32, device=index.device)
+    if not K.is_gpu(index.pts):
+        KERNELS_USED.add("cpu")
+        return K.radius_periodic_count_cpu(index.pts[:n], queries, cut2, per, qcut2)
+    qsorted, qperm = _sorted if _sorted is not None else prepare_queries(index, queries, locate=False)[:2]
+    raw = torch.zeros(K.RADIUS_PERIODIC_STATS, dtype=torch.int64, device=index.device) if stats is not None else None
+    counts = K.radius_periodic_count_gpu(index.tree(), qsorted, nq, cut2, qperm, per, qcut2=qcut2, stats=raw)
+    KERNELS_USED.add("radius_periodic")
+    if stats is not None:
+        for nm, v in zip(_RADIUS_PERIODIC_STATS, raw.cpu().tolist()):
+            stats.counters[nm] = stats.counters.get(nm, 0) + int(v)
+    return counts
+
+
+def _periodic_neighbors(what: str, index: LocalIndex, queries: torch.Tensor, cut2: float,
+                        qcut2: torch.Tensor | None, per: tuple, sort: bool, max_pairs: int) -> tuple:
+    nq, n = queries.shape[0], index.n
+    dev = index.device
+    gpu = K.is_gpu(index.pts)
+    if nq == 0 or n == 0:
+        return _empty_csr(nq, dev)
+    prep = prepare_queries(index, queries, locate=False)[:2] if gpu else None
+    counts = _periodic_counts(index, queries, cut2, qcut2, per, None, _sorted=prep)
+    offsets = torch.zeros(nq + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, dtype=torch.int64, out=offsets[1:])
+    total, longest = (int(v) for v in torch.stack((offsets[nq], counts.max().long())).tolist())  # the only sync
+    if total > max_pairs:
+        raise ValueError(f"{what}: {total} pairs within the radius exceed max_pairs = {max_pairs}; "
+                         "query fewer points at a time or raise max_pairs")
+    if not gpu:
+        o2, idx, d2 = K.radius_periodic_cpu(_input_order(index), queries, cut2, per, qcut2)
+        return o2, idx, K.finalize_distances(d2)
+    qsorted, qperm = prep
+    idx, dist, err = K.radius_periodic_fill_gpu(index.tree(), index.perm, qsorted, nq, cut2, qperm, offsets, total,
+                                                longest, per, qcut2=qcut2, sort=sort)
+    LAST_RADIUS_ERRORS[0] = int(err.item()) & 0xFFFFFFFF
+    if LAST_RADIUS_ERRORS[0]:
+        raise NativeError(f"{what}: {LAST_RADIUS_ERRORS[0]} rows were not filled to their count "
+                          "(the count pass and the fill pass disagree: a bug)")
+    return offsets, idx, dist
+
+
 def radius_counts(index: LocalIndex, queries: torch.Tensor, radius: float | torch.Tensor,
-                  stats: KnnStats | None = None, _sorted: tuple | None = None, squared: bool = False) -> torch.Tensor:
+                  stats: KnnStats | None = None, _sorted: tuple | None = None, squared: bool = False,
+                  period=None) -> torch.Tensor:
     """int32 [nq], in query order: for every row of `queries` (float32 [nq, 3] on the index's
     device) the number of points of `index` with dist2(q, p) < cut2_of(radius) — the strict
     comparison of the k-th-distance cutoff, so count >= k exactly when query_points with that
@@ -1185,7 +1306,19 @@ def radius_counts(index: LocalIndex, queries: torch.Tensor, radius: float | torc
     `radius` may be a float32 tensor [nq] on the index's device, one radius per query row
     (gather: p counts for q iff dist2(q, p) < cut2[q]); a negative or NaN entry raises
     ValueError before any kernel runs. squared=True: the given value(s) are the squared
-    cutoffs themselves (the engine's own squared distances can be handed back as they are)."""
+    cutoffs themselves (the engine's own squared distances can be handed back as they are).
+
+    period: one value L or (Lx, Ly, Lz), each > 0, inf = open axis: the box is periodic and
+    dist2 becomes the minimum image of the difference — per axis, in float32, d = q - p; d >
+    L/2: d - L; d < -L/2: d + L — so the distance is symmetric in its bits and a pair belongs to
+    one image. It is the physical periodic distance for coordinates inside one period
+    (wrap_points brings them there); no origin enters it. The radius (every entry) may not
+    exceed half the period of a finite axis: ValueError before any kernel runs, as for a bad
+    period. `stats` also receives radius_images, the image walks summed over the query groups.
+    None: the open box, the path without this argument."""
+    if period is not None:
+        per, queries, cut2, qcut2 = _period_cutoffs("radius_counts", index, queries, radius, squared, period)
+        return _periodic_counts(index, queries, cut2, qcut2, per, stats, _sorted=_sorted)
     if isinstance(radius, torch.Tensor):
         queries = _check_foreign("radius_counts", index, queries)
         qcut2 = _cut2_tensor("radius_counts", "radius", radius, queries.shape[0], index.device, squared)
@@ -1209,7 +1342,7 @@ def radius_counts(index: LocalIndex, queries: torch.Tensor, radius: float | torc
 
 
 def radius_neighbors(index: LocalIndex, queries: torch.Tensor, radius: float | torch.Tensor, sort: bool = True,
-                     max_pairs: int = 1 << 28, squared: bool = False) -> tuple:
+                     max_pairs: int = 1 << 28, squared: bool = False, period=None) -> tuple:
     """Fixed-radius neighbour lists in CSR form, in query order: (offsets int64 [nq + 1], idx
     int32 [total], dist float32 [total]). Row q = [offsets[q], offsets[q + 1]) holds every
     point of `index` with dist2(q, p) < cut2_of(radius) (see radius_counts), however many
@@ -1217,8 +1350,11 @@ def radius_neighbors(index: LocalIndex, queries: torch.Tensor, radius: float | t
     row ascending by (dist2 bits, row), the order of the neighbour lists, whatever the
     index's internal order; sort=False: unspecified order inside a row (cheaper). More than
     `max_pairs` pairs in all raise ValueError before anything is allocated for them.
-    `radius` may be a float32 tensor [nq], one radius per query row; `squared` as in
-    radius_counts."""
+    `radius` may be a float32 tensor [nq], one radius per query row; `squared` and `period`
+    as in radius_counts (under a period dist holds the periodic distances)."""
+    if period is not None:
+        per, queries, cut2, qcut2 = _period_cutoffs("radius_neighbors", index, queries, radius, squared, period)
+        return _periodic_neighbors("radius_neighbors", index, queries, cut2, qcut2, per, sort, max_pairs)
     if isinstance(radius, torch.Tensor):
         queries = _check_foreign("radius_neighbors", index, queries)
         qcut2 = _cut2_tensor("radius_neighbors", "radius", radius, queries.shape[0], index.device, squared)
@@ -1260,38 +1396,54 @@ def _check_radius(what: str, radius, nq: int, device: torch.device, squared: boo
 
 
 def radius_query_counts(points: torch.Tensor, queries: torch.Tensor, radius: float | torch.Tensor,
-                        stats: KnnStats | None = None, squared: bool = False) -> torch.Tensor:
+                        stats: KnnStats | None = None, squared: bool = False, period=None) -> torch.Tensor:
     """radius_counts over an index built once from `points` (both float32 [*, 3] on one
     device), in the points' own frame."""
     if points.device != queries.device:
         raise ValueError(f"radius_query_counts: points on {points.device}, queries on {queries.device}")
     if points.shape[0] == 0:  # nothing to index
+        if period is not None:
+            K.check_period("radius_query_counts", period)
         _check_radius("radius_query_counts", radius, queries.shape[0], queries.device, squared)
         return torch.zeros(queries.shape[0], dtype=torch.int32, device=queries.device)
+    if period is not None:
+        return radius_counts(build_index(points), queries, radius, stats=stats, squared=squared, period=period)
     return radius_counts(build_index(points), queries, radius, stats=stats, squared=squared)
 
 
 def radius_query_neighbors(points: torch.Tensor, queries: torch.Tensor, radius: float | torch.Tensor,
-                           sort: bool = True, max_pairs: int = 1 << 28, squared: bool = False) -> tuple:
+                           sort: bool = True, max_pairs: int = 1 << 28, squared: bool = False,
+                           period=None) -> tuple:
     """radius_neighbors over an index built once from `points`, in the points' own frame."""
     if points.device != queries.device:
         raise ValueError(f"radius_query_neighbors: points on {points.device}, queries on {queries.device}")
     if points.shape[0] == 0:  # nothing to index: every row is empty
+        if period is not None:
+            K.check_period("radius_query_neighbors", period)
         _check_radius("radius_query_neighbors", radius, queries.shape[0], queries.device, squared)
         return _empty_csr(queries.shape[0], queries.device)
+    if period is not None:
+        return radius_neighbors(build_index(points), queries, radius, sort=sort, max_pairs=max_pairs,
+                                squared=squared, period=period)
     return radius_neighbors(build_index(points), queries, radius, sort=sort, max_pairs=max_pairs, squared=squared)
 
 
 def radius_self_neighbors(points: torch.Tensor, radius: float | torch.Tensor, sort: bool = True,
-                          max_pairs: int = 1 << 28, squared: bool = False) -> tuple:
+                          max_pairs: int = 1 << 28, squared: bool = False, period=None) -> tuple:
     """radius_query_neighbors with the points as their own queries: for radius > 0 every
     sorted row starts with a point at distance 0 (itself, or the lowest row among its
     exact copies)."""
-    return radius_query_neighbors(points, points, radius, sort=sort, max_pairs=max_pairs, squared=squared)
+    return radius_query_neighbors(points, points, radius, sort=sort, max_pairs=max_pairs, squared=squared,
+                                  period=period)
+
+
+def _no_period(what: str, period) -> None:
+    if period is not None:
+        raise ValueError(f"{what}: a period is not supported for per-point radii")
 
 
 def point_radius_counts(index: LocalIndex, queries: torch.Tensor, point_radii, squared: bool = False,
-                        stats: KnnStats | None = None) -> torch.Tensor:
+                        stats: KnnStats | None = None, period=None) -> torch.Tensor:
     """int32 [nq], in query order: for every row of `queries` the number of points p of
     `index` whose own ball reaches it, dist2(q, p) < cut2[p] (scatter: "which points reach
     me"). point_radii: float32 [n] on the index's device in the order of the indexed array's
@@ -1299,16 +1451,19 @@ def point_radius_counts(index: LocalIndex, queries: torch.Tensor, point_radii, s
     index. A radius of 0 selects nothing, a point with radius inf is counted by every finite
     query; a negative or NaN entry raises ValueError before any kernel runs. The walk culls a
     node with the largest cutoff below it; there is no whole-box shortcut (it would need the
-    smallest cutoff below a node), so radius_box_accepts stays 0 in `stats`."""
+    smallest cutoff below a node), so radius_box_accepts stays 0 in `stats`. The scatter
+    searches have no periodic form: a `period` raises ValueError ("not supported")."""
+    _no_period("point_radius_counts", period)
     queries = _check_foreign("point_radius_counts", index, queries)
     prad = _point_radii("point_radius_counts", index, point_radii, squared)
     return _var_counts("point_radius_counts", index, queries, None, prad, stats)
 
 
 def point_radius_neighbors(index: LocalIndex, queries: torch.Tensor, point_radii, squared: bool = False,
-                           sort: bool = True, max_pairs: int = 1 << 28) -> tuple:
+                           sort: bool = True, max_pairs: int = 1 << 28, period=None) -> tuple:
     """The CSR lists of radius_neighbors under the per-point predicate of point_radius_counts:
     row q holds every point p of `index` with dist2(q, p) < cut2[p], in the same order."""
+    _no_period("point_radius_neighbors", period)
     queries = _check_foreign("point_radius_neighbors", index, queries)
     prad = _point_radii("point_radius_neighbors", index, point_radii, squared)
     return _var_neighbors("point_radius_neighbors", index, queries, None, prad, sort, max_pairs)
@@ -1321,24 +1476,28 @@ def _point_query_index(what: str, points: torch.Tensor, queries: torch.Tensor) -
 
 
 def point_radius_query_counts(points: torch.Tensor, queries: torch.Tensor, point_radii: torch.Tensor,
-                              squared: bool = False, stats: KnnStats | None = None) -> torch.Tensor:
+                              squared: bool = False, stats: KnnStats | None = None, period=None) -> torch.Tensor:
     """point_radius_counts over an index built once from `points`, in the points' own frame."""
+    _no_period("point_radius_query_counts", period)
     index = _point_query_index("point_radius_query_counts", points, queries)
     return point_radius_counts(index, queries, point_radii, squared=squared, stats=stats)
 
 
 def point_radius_query_neighbors(points: torch.Tensor, queries: torch.Tensor, point_radii: torch.Tensor,
-                                 squared: bool = False, sort: bool = True, max_pairs: int = 1 << 28) -> tuple:
+                                 squared: bool = False, sort: bool = True, max_pairs: int = 1 << 28,
+                                 period=None) -> tuple:
     """point_radius_neighbors over an index built once from `points`, in the points' own frame."""
+    _no_period("point_radius_query_neighbors", period)
     index = _point_query_index("point_radius_query_neighbors", points, queries)
     return point_radius_neighbors(index, queries, point_radii, squared=squared, sort=sort, max_pairs=max_pairs)
 
 
 def point_radius_self_neighbors(points: torch.Tensor, point_radii: torch.Tensor, squared: bool = False,
-                                sort: bool = True, max_pairs: int = 1 << 28) -> tuple:
+                                sort: bool = True, max_pairs: int = 1 << 28, period=None) -> tuple:
     """point_radius_query_neighbors with the points as their own queries: row i holds the
     points whose ball contains point i (with the k-th squared distances as squared radii, the
     points that have i among their k nearest, ties at the k-th distance left out)."""
+    _no_period("point_radius_self_neighbors", period)
     return point_radius_query_neighbors(points, points, point_radii, squared=squared, sort=sort, max_pairs=max_pairs)
 
 
@@ -1364,8 +1523,43 @@ def _cluster_args(what: str, eps: float, min_pts: int, squared: bool) -> tuple[f
     return cut2, int(min_pts)
 
 
+def _cluster_period(what: str, eps: float, cut2: float, squared: bool, period) -> tuple:
+    """The checked period of a clustering: eps may not exceed half the period of a finite axis
+    (r <= fl(0.5 L); squared: cut2 <= fl(h h)), which also keeps a tight node from wrapping
+    inside (periodic.hip)."""
+    return check_period_radius(what, eps, squared, period, name="eps")
+
+
+def _cluster_periodic(index: LocalIndex, cut2: float, min_pts: int, per: tuple,
+                      stats: KnnStats | None) -> tuple[torch.Tensor, torch.Tensor]:
+    """cluster_labels under a period (checked arguments, n >= 1)."""
+    n, dev = index.n, index.device
+    if not K.is_gpu(index.pts):
+        KERNELS_USED.add("cpu")
+        return K.cluster_periodic_cpu(_input_order(index), cut2, min_pts, per)
+    raw_r = torch.zeros(K.RADIUS_PERIODIC_STATS, dtype=torch.int64, device=dev) if stats is not None else None
+    raw_c = torch.zeros(K.CLUSTER_STATS, dtype=torch.int64, device=dev) if stats is not None else None
+    # counts in input order: the sorted points are their own queries, perm their rows
+    counts = K.radius_periodic_count_gpu(index.tree(), index.pts, n, cut2, index.perm, per, stats=raw_r)
+    core = counts >= min_pts
+    core_sorted = core[index.perm[:n].long()].to(torch.uint8)
+    labels, err = K.cluster_periodic_gpu(index.tree(), index.perm, core_sorted, cut2, per, fof=min_pts == 1,
+                                         border=min_pts > 1, half=CLUSTER_HALF, stats=raw_c)
+    KERNELS_USED.update(("radius_periodic", "cluster_periodic"))
+    LAST_CLUSTER_ERRORS[0] = int(err.item()) & 0xFFFFFFFF  # the only host read
+    if LAST_CLUSTER_ERRORS[0]:
+        raise NativeError(f"cluster_labels: {LAST_CLUSTER_ERRORS[0]} parent chains did not end "
+                          "(the union-find's invariant is broken: a bug)")
+    if stats is not None:
+        for nm, v in zip(_RADIUS_PERIODIC_STATS, raw_r.cpu().tolist()):
+            stats.counters[nm] = stats.counters.get(nm, 0) + int(v)
+        for nm, v in zip(_CLUSTER_STATS, raw_c.cpu().tolist()):
+            stats.counters[nm] = stats.counters.get(nm, 0) + int(v)
+    return labels, core
+
+
 def cluster_labels(index: LocalIndex, eps: float, min_pts: int = 1, squared: bool = False,
-                   stats: KnnStats | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+                   stats: KnnStats | None = None, period=None) -> tuple[torch.Tensor, torch.Tensor]:
     """Density clustering of the points of `index`: (labels int32 [n], core bool [n]) in the
     order of the indexed array's rows. Friends-of-friends for min_pts = 1, DBSCAN otherwise.
 
@@ -1386,14 +1580,22 @@ def cluster_labels(index: LocalIndex, eps: float, min_pts: int = 1, squared: boo
     walks the tree (cluster.hip), so memory is O(n) whatever the density. eps < 0, NaN eps or
     min_pts < 1 raise ValueError before any kernel runs; an index built in a rotated frame
     raises too. One host read (the device error word). `stats` receives cluster_evals /
-    _nodes / _buckets / _clique_accepts / _cas_retries and the count pass's radius_* counters."""
+    _nodes / _buckets / _clique_accepts / _cas_retries and the count pass's radius_* counters.
+
+    period (one value or three, inf = open axis; see radius_counts): the box is periodic, two
+    points are linked iff the minimum-image squared distance is below the cutoff, so a group
+    that straddles a face stays one group. eps may not exceed half the period of a finite axis
+    (ValueError). None: the open box, the path without this argument."""
     cut2, min_pts = _cluster_args("cluster_labels", eps, min_pts, squared)
+    per = _cluster_period("cluster_labels", eps, cut2, squared, period) if period is not None else None
     if index.qrot is not None:
         raise ValueError("cluster_labels: an index built in a rotated frame cannot be clustered "
                          "(build_index(points) without a frame)")
     n, dev = index.n, index.device
     if n == 0:
         return torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.bool, device=dev)
+    if per is not None:
+        return _cluster_periodic(index, cut2, min_pts, per, stats)
     if not K.is_gpu(index.pts):
         KERNELS_USED.add("cpu")
         return K.cluster_cpu(_input_order(index), cut2, min_pts)
@@ -1418,15 +1620,19 @@ def cluster_labels(index: LocalIndex, eps: float, min_pts: int = 1, squared: boo
 
 
 def cluster_points(points: torch.Tensor, eps: float, min_pts: int = 1, squared: bool = False,
-                   stats: KnnStats | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+                   stats: KnnStats | None = None, period=None) -> tuple[torch.Tensor, torch.Tensor]:
     """cluster_labels over an index built once from `points` (float32 [n, 3]), in the points'
     own frame."""
-    _cluster_args("cluster_points", eps, min_pts, squared)
+    cut2, _ = _cluster_args("cluster_points", eps, min_pts, squared)
+    if period is not None:
+        _cluster_period("cluster_points", eps, cut2, squared, period)
     if points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32:
         raise ValueError("cluster_points: points must be a float32 [n, 3] tensor")
     if points.shape[0] == 0:  # nothing to index
         return (torch.empty(0, dtype=torch.int32, device=points.device),
                 torch.empty(0, dtype=torch.bool, device=points.device))
+    if period is not None:
+        return cluster_labels(build_index(points), eps, min_pts, squared=squared, stats=stats, period=period)
     return cluster_labels(build_index(points), eps, min_pts, squared=squared, stats=stats)
 
 

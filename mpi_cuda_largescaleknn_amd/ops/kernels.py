@@ -894,6 +894,179 @@ def cluster_gpu(tree: tuple, perm: torch.Tensor, core_sorted: torch.Tensor, cut2
     return labels, err
 
 
+# --------------------------------------------------------------------------- periodic box
+RADIUS_PERIODIC_STATS = 5  # periodic.hip: the four of radius.hip and the image walks
+
+
+def check_period(what: str, period) -> tuple[float, float, float]:
+    """(Lx, Ly, Lz) as float32 values: a scalar is broadcast; every entry > 0, inf = open axis.
+    Anything else (NaN, <= 0, not one or three values) raises ValueError."""
+    if isinstance(period, torch.Tensor):
+        period = period.detach().cpu().tolist()
+    if isinstance(period, (int, float)) and not isinstance(period, bool):
+        period = (period,) * 3
+    try:
+        vals = tuple(float(torch.tensor(float(v), dtype=torch.float32)) for v in period)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: period must be one value or three (got {period!r})") from None
+    if len(vals) != 3:
+        raise ValueError(f"{what}: period must be one value or three (got {len(vals)})")
+    if not all(v > 0.0 for v in vals):  # (a NaN fails the comparison too)
+        raise ValueError(f"{what}: every period entry must be > 0 (inf: open axis), got {vals}")
+    return vals
+
+
+def period_cut2_bound(period: tuple[float, float, float]) -> float:
+    """The largest squared cutoff a period admits: the smallest fl(h * h), h = fl(0.5 L), over its
+    finite axes (inf when every axis is open), in float32 arithmetic."""
+    L = torch.tensor(period, dtype=torch.float32)
+    h = L * 0.5
+    return float((h * h).min())
+
+
+def _period_c(period: tuple[float, float, float]):
+    return (C.c_float * 3)(*period)
+
+
+def radius_periodic_count_cpu(points: torch.Tensor, queries: torch.Tensor, cut2: float, period,
+                              qcut2: torch.Tensor | None = None) -> torch.Tensor:
+    """CPU oracle (brute force) of the periodic counts: radius_count_cpu with dist2 replaced by the
+    minimum image of the difference under `period` (per axis d = q - p; d > L/2: d - L; d <
+    -L/2: d + L, in float32), strict. qcut2 (float32 [nq]) replaces cut2 per query."""
+    per = check_period("radius_periodic_count_cpu", period)
+    pts = points.contiguous().float().cpu()
+    q = queries.contiguous().float().cpu()
+    qc = _var_cut2_cpu("radius_periodic_count_cpu", qcut2, q.shape[0])
+    counts = torch.empty(q.shape[0], dtype=torch.int32)
+    _native.host().lsk_cpu_radius_periodic_count(_ptr(pts), pts.shape[0], _ptr(q), q.shape[0], C.c_float(cut2),
+                                                 _ptr(qc), _period_c(per), _ptr(counts), _nthreads())
+    return counts
+
+
+def radius_periodic_cpu(points: torch.Tensor, queries: torch.Tensor, cut2: float, period,
+                        qcut2: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """CPU oracle of the periodic radius lists, the CSR form and row order of radius_cpu under the
+    predicate of radius_periodic_count_cpu (d2: the periodic squared distances)."""
+    per = check_period("radius_periodic_cpu", period)
+    pts = points.contiguous().float().cpu()
+    q = queries.contiguous().float().cpu()
+    nq = q.shape[0]
+    qc = _var_cut2_cpu("radius_periodic_cpu", qcut2, nq)
+    offsets = torch.zeros(nq + 1, dtype=torch.int64)
+    torch.cumsum(radius_periodic_count_cpu(pts, q, cut2, per, qc), 0, dtype=torch.int64, out=offsets[1:])
+    total = int(offsets[nq])
+    idx = torch.empty(total, dtype=torch.int32)
+    d2 = torch.empty(total, dtype=torch.float32)
+    _native.host().lsk_cpu_radius_periodic_fill(_ptr(pts), pts.shape[0], _ptr(q), nq, C.c_float(cut2), _ptr(qc),
+                                                _period_c(per), _ptr(offsets), _ptr(idx), _ptr(d2), _nthreads())
+    return offsets, idx, d2
+
+
+def cluster_periodic_cpu(points: torch.Tensor, cut2: float, min_pts: int = 1,
+                         period=math.inf) -> tuple[torch.Tensor, torch.Tensor]:
+    """CPU oracle of the periodic density clustering: cluster_cpu with the periodic squared
+    distance of radius_periodic_count_cpu."""
+    if min_pts < 1 or not cut2 >= 0.0:
+        raise ValueError("cluster_periodic_cpu: min_pts must be at least 1 and cut2 >= 0")
+    per = check_period("cluster_periodic_cpu", period)
+    pts = points.contiguous().float().cpu()
+    n = pts.shape[0]
+    labels = torch.empty(n, dtype=torch.int32)
+    core = torch.empty(n, dtype=torch.uint8)
+    _native.host().lsk_cpu_cluster_periodic(_ptr(pts), n, C.c_float(cut2), int(min_pts), _period_c(per),
+                                            _ptr(labels), _ptr(core), _nthreads())
+    return labels, core.bool()
+
+
+def _periodic_view(what: str, tree: tuple, qsorted: torch.Tensor, nq: int, out_perm: torch.Tensor,
+                   cut2: float, qcut2: torch.Tensor | None):
+    if qcut2 is None:
+        if not cut2 >= 0.0:
+            raise ValueError(f"{what}: cut2 must be >= 0")
+    elif qcut2.dtype != torch.float32 or qcut2.shape != (nq,) or not qcut2.is_contiguous() \
+            or qcut2.device != tree[0].device:
+        raise ValueError(f"{what}: qcut2 float32 [{nq}], contiguous, on the tree's device")
+    return _walk_view(what, tree, qsorted, nq, out_perm)
+
+
+def radius_periodic_count_gpu(tree: tuple, qsorted: torch.Tensor, nq: int, cut2: float, out_perm: torch.Tensor,
+                              period: tuple[float, float, float], qcut2: torch.Tensor | None = None,
+                              stats: torch.Tensor | None = None) -> torch.Tensor:
+    """The count pass of the periodic radius search (periodic.hip), as radius_count_gpu. period:
+    check_period's values; qcut2: float32 [nq] squared cutoffs in query order in place of cut2
+    (entries >= 0, no NaN, within the period's bound: the caller checks). stats: optional zeroed
+    int64 [RADIUS_PERIODIC_STATS]."""
+    tv = _periodic_view("radius_periodic_count_gpu", tree, qsorted, nq, out_perm, cut2, qcut2)
+    counts = torch.empty(nq, dtype=torch.int32, device=tree[0].device)
+    check(_native.hip().lsk_hip_radius_periodic_count(C.byref(tv), _ptr(qsorted), int(nq), C.c_float(cut2),
+                                                      _ptr(qcut2), _period_c(period), _ptr(out_perm), _ptr(counts),
+                                                      _ptr(stats), _stream(tree[0])), "radius_periodic_count")
+    return counts
+
+
+def radius_periodic_fill_gpu(tree: tuple, perm: torch.Tensor, qsorted: torch.Tensor, nq: int, cut2: float,
+                             out_perm: torch.Tensor, offsets: torch.Tensor, total: int, longest: int,
+                             period: tuple[float, float, float], qcut2: torch.Tensor | None = None,
+                             sort: bool = True) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The fill and sort passes of the periodic radius search, as radius_fill_gpu (the sort is
+    lsk_hip_radius_sort itself); period / qcut2 as for radius_periodic_count_gpu."""
+    tv = _periodic_view("radius_periodic_fill_gpu", tree, qsorted, nq, out_perm, cut2, qcut2)
+    dev = tree[0].device
+    if offsets.dtype != torch.int64 or offsets.numel() != nq + 1 or not offsets.is_contiguous() or offsets.device != dev \
+            or perm.dtype != torch.int32 or perm.numel() < tree[3] or not perm.is_contiguous() or perm.device != dev:
+        raise ValueError("radius_periodic_fill_gpu: offsets int64 [nq + 1] and perm int32 [n], contiguous, "
+                         "on the tree's device")
+    lib = _native.hip()
+    idx = torch.empty(total, dtype=torch.int32, device=dev)
+    dist = torch.empty(total, dtype=torch.float32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    check(lib.lsk_hip_radius_periodic_fill(C.byref(tv), _ptr(perm), _ptr(qsorted), int(nq), C.c_float(cut2),
+                                           _ptr(qcut2), _period_c(period), _ptr(out_perm), _ptr(offsets), _ptr(idx),
+                                           _ptr(dist), _ptr(err), _stream(tree[0])), "radius_periodic_fill")
+    check(lib.lsk_hip_radius_sort(_ptr(offsets), int(nq), int(total), int(longest), _ptr(idx), _ptr(dist),
+                                  1 if sort else 0, _stream(tree[0])), "radius_sort")
+    return idx, dist, err
+
+
+def cluster_periodic_gpu(tree: tuple, perm: torch.Tensor, core_sorted: torch.Tensor, cut2: float,
+                         period: tuple[float, float, float], fof: bool, border: bool, half: bool = False,
+                         stats: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """cluster_gpu under a period: the init, flatten, min-row and label passes of cluster.hip
+    around the periodic hook and border walks of periodic.hip. core_sorted comes from the
+    periodic count."""
+    pts, nodes, qnodes, n, depth = tree
+    dev = pts.device
+    if not cut2 >= 0.0:
+        raise ValueError("cluster_periodic_gpu: cut2 must be >= 0")
+    for t, dt in ((perm, torch.int32), (core_sorted, torch.uint8)):
+        if t.dtype != dt or t.numel() < n or not t.is_contiguous() or t.device != dev:
+            raise ValueError("cluster_periodic_gpu: perm int32 [n] and core_sorted uint8 [n], contiguous, "
+                             "on the tree's device")
+    if stats is not None and (stats.dtype != torch.int64 or stats.numel() < CLUSTER_STATS or stats.device != dev):
+        raise ValueError(f"cluster_periodic_gpu: stats int64 [{CLUSTER_STATS}] on the tree's device")
+    tv = TreeView(_ptr(pts), _ptr(nodes), _ptr(qnodes), n, depth, 0)
+    cpre = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+    torch.cumsum(core_sorted[:n], 0, dtype=torch.int32, out=cpre[1:])
+    parent = torch.empty(n, dtype=torch.int32, device=dev)
+    root = torch.empty(n, dtype=torch.int32, device=dev)
+    minrow = torch.empty(n, dtype=torch.int32, device=dev)
+    labels = torch.empty(n, dtype=torch.int32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    lib, st, per = _native.hip(), _stream(pts), _period_c(period)
+    check(lib.lsk_hip_cluster_init(C.byref(tv), _ptr(core_sorted), _ptr(cpre), C.c_float(cut2), _ptr(parent),
+                                   _ptr(minrow), st), "cluster_init")
+    check(lib.lsk_hip_cluster_periodic_hook(C.byref(tv), _ptr(core_sorted), _ptr(cpre), C.c_float(cut2), per,
+                                            1 if half else 0, _ptr(parent), _ptr(err), _ptr(stats), st),
+          "cluster_periodic_hook")
+    check(lib.lsk_hip_cluster_label(C.byref(tv), _ptr(perm), _ptr(core_sorted), _ptr(parent), 1 if fof else 0,
+                                    _ptr(root), _ptr(minrow), _ptr(labels), _ptr(err), st), "cluster_label")
+    if border:
+        check(lib.lsk_hip_cluster_periodic_border(C.byref(tv), _ptr(perm), _ptr(core_sorted), C.c_float(cut2), per,
+                                                  _ptr(root), _ptr(minrow), _ptr(labels), _ptr(stats), st),
+              "cluster_periodic_border")
+    return labels, err
+
+
 # --------------------------------------------------------------------------- halo
 UB_MAX_W = 8  # tree.hip kUbMaxW: beyond it the box-pair bound
 

@@ -5,6 +5,7 @@ points at the same eps.
     python scripts/cluster_bench.py [--data uniform|clustered|duplicates] [--points N]
                                     [--f 0.2,0.9,2.0] [--min-pts 1,5] [--steps 5] [--warmup 2]
                                     [--no-half] [--counts-only] [--package-root DIR]
+                                    [--period L | Lx,Ly,Lz]
 
 eps = f x extent x n^(-1/3) (f = 0.9 is near percolation for uniform points, 2.0 one giant
 component). For every (f, min_pts), on one index, device-synchronised host clock, medians
@@ -19,7 +20,9 @@ per configuration with the times, the ratios, clusters / core / noise counts and
 counters (CAS retries per point, clique acceptances). 64 sampled core flags are checked against
 radius_count_cpu. --counts-only times nothing but `counts` and imports nothing newer than
 radius_counts, so that with --package-root it measures another checkout of the package (the
-parent commit) on the same data. --no-half: see knn_engine.CLUSTER_HALF.
+parent commit) on the same data. --no-half: see knn_engine.CLUSTER_HALF. --period: the data is
+wrapped into [0, L) (wrap_points) and every case searches the periodic box; the JSON then also
+carries radius_images / groups of the count pass.
 """
 from __future__ import annotations
 
@@ -58,6 +61,7 @@ def main() -> int:
     ap.add_argument("--no-half", action="store_true")
     ap.add_argument("--counts-only", action="store_true")
     ap.add_argument("--package-root", default=ROOT)
+    ap.add_argument("--period", default="", metavar="L | Lx,Ly,Lz")
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.package_root))
     import torch
@@ -70,6 +74,11 @@ def main() -> int:
     fs = [float(v) for v in (a.f or ("0.2,0.9,2.0" if a.data == "uniform" else "0.5")).split(",")]
     dev = torch.device("cuda", 0)
     p = make(a.data, n, dev)
+    per = {}  # (no --period: the calls without the keyword)
+    if a.period:
+        vals = [float(v) for v in a.period.split(",")]
+        per = {"period": K.check_period("--period", vals * 3 if len(vals) == 1 else vals)}
+        p = E.wrap_points(p, per["period"]).contiguous()
     extent = float((p.max(0).values - p.min(0).values).max())
     index = E.build_index(p)
     if a.no_half:
@@ -77,16 +86,16 @@ def main() -> int:
     ok = True
     for f in fs:
         eps = f * extent * n ** (-1.0 / 3.0)
-        counts = E.radius_counts(index, p, eps)
+        counts = E.radius_counts(index, p, eps, **per)
         pairs = int(counts.sum(dtype=torch.int64))
         for min_pts in ([0] if a.counts_only else [int(v) for v in a.min_pts.split(",")]):
             out = {}
-            cases = {"counts": lambda: out.__setitem__("c", E.radius_counts(index, p, eps))}
+            cases = {"counts": lambda: out.__setitem__("c", E.radius_counts(index, p, eps, **per))}
             if not a.counts_only:
-                cases["cluster"] = lambda: out.__setitem__("l", E.cluster_labels(index, eps, min_pts))
+                cases["cluster"] = lambda: out.__setitem__("l", E.cluster_labels(index, eps, min_pts, **per))
                 if pairs <= a.max_pairs:
                     cases["lists"] = lambda: out.__setitem__("n", E.radius_neighbors(index, p, eps, sort=False,
-                                                                                      max_pairs=a.max_pairs))
+                                                                                      max_pairs=a.max_pairs, **per))
             times = {name: [] for name in cases}
             for step in range(a.warmup + a.steps):
                 for name, fn in cases.items():
@@ -103,9 +112,13 @@ def main() -> int:
                    "spread": {name: [min(ts), max(ts)] for name, ts in times.items()}}
             if not a.counts_only:
                 stats = E.KnnStats()
-                labels, core = E.cluster_labels(index, eps, min_pts, stats=stats)
+                labels, core = E.cluster_labels(index, eps, min_pts, stats=stats, **per)
                 smp = torch.randint(0, n, (64,), generator=torch.Generator().manual_seed(3))
-                ref = K.radius_count_cpu(p.cpu(), p[smp.to(dev)].cpu(), E.cut2_of(eps)) >= min_pts
+                if per:
+                    ref = K.radius_periodic_count_cpu(p.cpu(), p[smp.to(dev)].cpu(), E.cut2_of(eps),
+                                                      per["period"]) >= min_pts
+                else:
+                    ref = K.radius_count_cpu(p.cpu(), p[smp.to(dev)].cpu(), E.cut2_of(eps)) >= min_pts
                 exact = int((core[smp.to(dev)].cpu() == ref).sum())
                 ok = ok and exact == 64
                 dense, nclusters = E.compact_labels(labels)
@@ -122,6 +135,10 @@ def main() -> int:
                     "cluster_evals_per_point": c["cluster_evals"] / n, "count_evals_per_point": c["radius_evals"] / n,
                     "sampled_core_exact": f"{exact}/64",
                 })
+                if per:
+                    groups = (n + 63) // 64
+                    rec.update({"period": list(per["period"]), "radius_images": c["radius_images"], "groups": groups,
+                                "images_per_group": c["radius_images"] / groups})
             print(json.dumps(rec), flush=True)
     return 0 if ok else 1
 

@@ -3,6 +3,7 @@
 
     python scripts/radius_bench.py [--points 1e7] [--queries 1e6] [--mean 100] [--steps 5] [--warmup 2]
                                    [--radii scalar|query-equal|query-loguniform|query-kth|point-kth]
+                                   [--period L | Lx,Ly,Lz]
 
 Uniform points in the unit cube and uniform queries from another seed; the radius is the one
 whose ball holds --mean points at the data's density (queries near the faces see fewer, so
@@ -20,6 +21,9 @@ step so that drift on a shared host hits them alike:
   * query-kth:        per-query radii 1.3 x the query's k-th neighbour distance, k = --kth;
   * point-kth:        per-point radii = every point's own k-th neighbour distance (scatter:
                       the reverse-neighbour search), prepared once outside the timed region.
+--period: the three radius cases search the periodic box (the unit cube holds the data, so 1 is
+the extent; not with point-kth); the JSON then carries radius_images / groups, the image
+walks per query group of the count pass, beside the times.
 Prints one JSON line. Sampled rows are checked against brute force.
 """
 from __future__ import annotations
@@ -37,6 +41,7 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
+from mpi_cuda_largescaleknn_amd.apps.radius import add_period_option  # noqa: E402
 from mpi_cuda_largescaleknn_amd.models import knn_engine as E  # noqa: E402
 from mpi_cuda_largescaleknn_amd.ops import kernels as K  # noqa: E402
 
@@ -51,7 +56,11 @@ def main() -> int:
     ap.add_argument("--radii", default="scalar",
                     choices=["scalar", "query-equal", "query-loguniform", "query-kth", "point-kth"])
     ap.add_argument("--kth", type=int, default=32, help="k of the k-th-distance radii (query-kth, point-kth)")
+    add_period_option(ap)
     a = ap.parse_args()
+    if a.period is not None and a.radii == "point-kth":
+        ap.error("--period is not supported with --radii point-kth")
+    per = {} if a.period is None else {"period": a.period}  # (none: the calls without the keyword)
     if not torch.cuda.is_available():
         sys.stderr.write("radius_bench: needs a GPU (a CPU timing says nothing about it)\n")
         return 2
@@ -84,8 +93,8 @@ def main() -> int:
             rad = 1.3 * E.query_points(index, q, E.KnnConfig(k=a.kth))
         if a.radii != "scalar":
             qc2 = rad * rad
-        counts_fn = lambda: E.radius_counts(index, q, rad)  # noqa: E731
-        lists_fn = lambda sort=True: E.radius_neighbors(index, q, rad, sort=sort)  # noqa: E731
+        counts_fn = lambda **kw: E.radius_counts(index, q, rad, **per, **kw)  # noqa: E731
+        lists_fn = lambda sort=True: E.radius_neighbors(index, q, rad, sort=sort, **per)  # noqa: E731
     cases = {
         "counts": lambda: out.__setitem__("counts", counts_fn()),
         "sorted": lambda: out.__setitem__("sorted", lists_fn()),
@@ -108,7 +117,10 @@ def main() -> int:
     counts = counts_fn()
     total = int(offsets[-1])
     smp = torch.randint(0, nq, (64,), generator=torch.Generator().manual_seed(3))
-    if a.radii == "scalar":
+    if a.period is not None:
+        ro, ri, rd2 = K.radius_periodic_cpu(p.cpu(), q[smp.to(dev)].cpu(), E.cut2_of(r), a.period,
+                                            None if qc2 is None else qc2[smp.to(dev)].cpu())
+    elif a.radii == "scalar":
         ro, ri, rd2 = K.radius_cpu(p.cpu(), q[smp.to(dev)].cpu(), E.cut2_of(r))
     else:
         ro, ri, rd2 = K.radius_var_cpu(p.cpu(), q[smp.to(dev)].cpu(), None if qc2 is None else qc2[smp.to(dev)].cpu(),
@@ -130,6 +142,12 @@ def main() -> int:
         "sorted_Mpairs_per_s": total / med["sorted"] / 1e6, "counts_Mqueries_per_s": nq / med["counts"] / 1e6,
         "sampled_exact": f"{exact}/64", "offsets_are_count_sums": consistent,
     }
+    if a.period is not None:
+        st = E.KnnStats()
+        counts_fn(stats=st)
+        groups = (nq + 63) // 64
+        rec.update({"period": list(a.period), "radius_images": st.counters["radius_images"], "groups": groups,
+                    "images_per_group": st.counters["radius_images"] / groups})
     print(json.dumps(rec), flush=True)
     return 0 if exact == 64 and consistent else 1
 
