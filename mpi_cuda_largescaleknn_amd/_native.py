@@ -58,7 +58,7 @@ class TreeView(C.Structure):
     ]
 
 
-HIP_ABI = 13  # lsk_hip_abi_version() of a library matching the structs below
+HIP_ABI = 14  # lsk_hip_abi_version() of a library matching the structs below
 
 
 class KnnArgs(C.Structure):
@@ -148,6 +148,10 @@ def _declare_host(lib: C.CDLL) -> None:
     lib.lsk_cpu_radius_periodic_fill.restype = None
     lib.lsk_cpu_cluster_periodic.argtypes = [vp, i64, C.c_float, i32, vp, vp, vp, i32]
     lib.lsk_cpu_cluster_periodic.restype = None
+    lib.lsk_cpu_kth_periodic.argtypes = [vp, i64, vp, i64, i32, C.c_float, vp, vp, i32]
+    lib.lsk_cpu_kth_periodic.restype = None
+    lib.lsk_cpu_knn_periodic.argtypes = [vp, i64, vp, i64, i32, C.c_float, vp, vp, vp, i32]
+    lib.lsk_cpu_knn_periodic.restype = None
     lib.lsk_cpu_count_below.argtypes = [vp, i64, vp, vp, i32, vp, i32]
     lib.lsk_cpu_count_below.restype = None
     lib.lsk_cpu_bounds.argtypes = [vp, i64, vp, i32]
@@ -214,6 +218,10 @@ def _declare_hip(lib: C.CDLL) -> None:
                                           vp], i32),
         "lsk_hip_cluster_periodic_hook": ([C.POINTER(TreeView), vp, vp, C.c_float, vp, i32, vp, vp, vp, vp], i32),
         "lsk_hip_cluster_periodic_border": ([C.POINTER(TreeView), vp, vp, C.c_float, vp, vp, vp, vp, vp, vp], i32),
+        "lsk_hip_pknn_flag": ([C.POINTER(TreeView), vp, vp, i64, C.c_float, vp, vp, vp, vp], i32),
+        "lsk_hip_pknn_count": ([C.POINTER(TreeView), vp, vp, i64, vp, vp, vp, vp, vp], i32),
+        "lsk_hip_pknn_fill": ([C.POINTER(TreeView), vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp], i32),
+        "lsk_hip_pknn_take": ([vp, i64, vp, vp, vp, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp], i32),
         "lsk_hip_grid_decide": ([vp, vp, i64, i32, C.c_float, i32, vp, vp], i32),
         "lsk_hip_boundary_groups": ([vp, i32, i64, vp, vp, vp, C.c_int, C.c_int, vp, vp], i32),
         "lsk_hip_grid_build": ([vp, vp, i64, vp, i32, vp, vp], i32),

@@ -6,6 +6,7 @@
     python -m mpi_cuda_largescaleknn_amd.apps.tools check in.float3 dist.float -k K [-r R] [--samples S]
            [--queries q.float3]  (dist.float then holds hipKNN_query's output for q.float3)
            [--neighbors PREFIX]  (also PREFIX.ids / PREFIX.dist of hipKNN_query --neighbors)
+           [--period L | Lx,Ly,Lz]  (with --queries: hipKNN_query --period, the periodic oracle)
            -> exact CPU oracle on sampled points, bitwise compare (replaces the reference's
               disabled '#if 0' RES dump, unorderedDataVariant.cu:215-227)
     python -m mpi_cuda_largescaleknn_amd.apps.tools rcheck in.float3 q.float3 PREFIX [--samples S]
@@ -86,9 +87,15 @@ def check(a) -> int:
     if dist.shape[0] != n:
         print(f"size mismatch: {dist.shape[0]} distances for {n} {'queries' if a.queries else 'points'}")
         return 1
+    if a.period is not None and not a.queries:
+        print("check: --period needs --queries (the periodic k-NN serves hipKNN_query only)")
+        return 1
     g = torch.Generator().manual_seed(0)
     idx = torch.randint(0, n, (min(a.samples, n),), generator=g) if a.samples < n else torch.arange(n)
-    ref = K.finalize_distances(K.kth_cpu(pts, qry[idx], a.k, cut2_of(a.r), "brute" if a.queries else "kdtree"))
+    if a.period is not None:
+        ref = K.finalize_distances(K.kth_periodic_cpu(pts, qry[idx], a.k, cut2_of(a.r), a.period))
+    else:
+        ref = K.finalize_distances(K.kth_cpu(pts, qry[idx], a.k, cut2_of(a.r), "brute" if a.queries else "kdtree"))
     got = dist[idx]
     bad = int((got != ref).sum())
     print(f"checked {idx.numel()} sampled points: {bad} mismatches")
@@ -107,7 +114,10 @@ def _check_neighbors(a, pts, qry, idx) -> int:
     if ids.shape[0] != n or nd.shape[0] != n:
         print(f"size mismatch: {ids.shape[0]} id rows, {nd.shape[0]} distance rows for {n} queries")
         return 1
-    ref_i, ref_d2 = K.knn_cpu(pts, qry[idx], a.k, cut2_of(a.r))
+    if a.period is not None:
+        ref_i, ref_d2 = K.knn_periodic_cpu(pts, qry[idx], a.k, cut2_of(a.r), a.period)
+    else:
+        ref_i, ref_d2 = K.knn_cpu(pts, qry[idx], a.k, cut2_of(a.r))
     ref_d = K.finalize_distances(ref_d2.view(-1)).view(-1, a.k)
     wrong = ((ids[idx] != ref_i) | (nd[idx] != ref_d)).any(dim=1)
     bad = int(wrong.sum())
@@ -293,11 +303,12 @@ def main(argv=None) -> int:
     p.add_argument("--queries", default=None, help="float3 file whose rows the distances belong to (hipKNN_query)")
     p.add_argument("--neighbors", default=None, metavar="PREFIX",
                    help="also check PREFIX.ids / PREFIX.dist (hipKNN_query --neighbors)")
+    from .radius import add_period_option, add_radius_options
+    add_period_option(p)
     p = sub.add_parser("rcheck")
     p.add_argument("inp")
     p.add_argument("queries")
     p.add_argument("prefix", help="the -o PREFIX of hipKNN_radius")
-    from .radius import add_period_option, add_radius_options
     add_radius_options(p)
     p.add_argument("--samples", type=int, default=1000)
     p.add_argument("--counts-only", action="store_true")

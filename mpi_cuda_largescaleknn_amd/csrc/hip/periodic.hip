@@ -48,161 +48,14 @@
 // cut2) has extent a per axis with fl(a a) <= dist2(diagonal) < cut2 <= fl(h h), and fl(a a)
 // < fl(h h) implies a < h: no pair inside wraps, pd2 is the open-box d², and the clique
 // pre-linking of cluster_init_kernel holds unchanged.
-#include "cluster_uf.h"
+#include "periodic_image.h"
 
 namespace {
 
 using lsk::fbits;
+using namespace lsk::periodic;
 
 constexpr int kWaves = 4;           // waves per block, one query group each (as radius.hip)
-constexpr float kSlack = 0x1p-21f;  // see "The cull is conservative"
-
-// One axis of the period as a group sees it (wave-uniform).
-struct Axis {
-  float L, h, e;  // period, half period, slack of a shifted gap
-  bool neg, pos;  // some pair (group query, root point) may take s = -1 / s = +1
-};
-
-__device__ __forceinline__ Axis make_axis(float L, float qlo, float qhi, float plo, float phi) {
-  Axis a;
-  a.L = L;
-  a.h = 0.5f * L;
-  a.neg = qhi - plo > a.h;
-  a.pos = qlo - phi < -a.h;
-  a.e = kSlack * (fmaxf(fabsf(qlo), fabsf(qhi)) + fmaxf(fabsf(plo), fabsf(phi)) + L);
-  return a;
-}
-
-// The shift of one axis in the current image: s, the offset o = s L of the query and the
-// slack e of the axis' gap (both 0 where s = 0, so that image 0 is the open-box arithmetic).
-struct Shift {
-  int s;
-  float o, e;
-};
-
-__device__ __forceinline__ bool shift_of(const Axis &a, int s, Shift &S) {
-  S.s = s;
-  S.o = 0.f;
-  S.e = 0.f;
-  if (s == 0) return true;
-  if (s < 0 ? !a.neg : !a.pos) return false;
-  S.o = s < 0 ? -a.L : a.L;
-  S.e = a.e;
-  return true;
-}
-
-struct Image {
-  Shift x, y, z;
-};
-
-// Image im in [0, 27) of the group, or false when no pair can take it.
-__device__ __forceinline__ bool image_of(const Axis &X, const Axis &Y, const Axis &Z, int im, Image &I) {
-  const int sx = im % 3 - 1, sy = (im / 3) % 3 - 1, sz = im / 9 - 1;
-  const bool ok_x = shift_of(X, sx, I.x), ok_y = shift_of(Y, sy, I.y), ok_z = shift_of(Z, sz, I.z);
-  return ok_x && ok_y && ok_z;
-}
-
-// The minimum image of one difference and the branch it took.
-__device__ __forceinline__ float wrap1(float d, float L, float h, int &w) {
-  w = 0;
-  if (d > h) {
-    d = d - L;
-    w = -1;
-  } else if (d < -h) {
-    d = d + L;
-    w = 1;
-  }
-  return d;
-}
-
-// Gap of one axis between the query range [qlo, qhi] moved by the image and [lo, hi].
-__device__ __forceinline__ float gap1(float qlo, float qhi, float lo, float hi, const Shift &S) {
-  const float g = fmaxf(fmaxf(lo - (qhi + S.o), (qlo + S.o) - hi), 0.f);
-  return fmaxf(g - S.e, 0.f);
-}
-
-__device__ __forceinline__ float image_box_dist2(const lsk::box3f &gb, const float4 &lo4, const float4 &hi4,
-                                                 const Image &I) {
-  return lsk::dist2(gap1(gb.lo.x, gb.hi.x, lo4.x, hi4.x, I.x), gap1(gb.lo.y, gb.hi.y, lo4.y, hi4.y, I.y),
-                    gap1(gb.lo.z, gb.hi.z, lo4.z, hi4.z, I.z));
-}
-
-__device__ __forceinline__ float image_point_dist2(const lsk::GroupQuery &Q, const float4 &lo4, const float4 &hi4,
-                                                   const Image &I) {
-  return lsk::dist2(gap1(Q.x, Q.x, lo4.x, hi4.x, I.x), gap1(Q.y, Q.y, lo4.y, hi4.y, I.y),
-                    gap1(Q.z, Q.z, lo4.z, hi4.z, I.z));
-}
-
-// One axis of the whole-box acceptance: both corners take branch s; f = the larger |wrapped
-// corner difference|.
-__device__ __forceinline__ bool far1(float q, float lo, float hi, const Axis &a, int s, float &f) {
-  int wl, wh;
-  const float dl = wrap1(q - lo, a.L, a.h, wl), dh = wrap1(q - hi, a.L, a.h, wh);
-  f = fmaxf(fabsf(dl), fabsf(dh));
-  return wl == s && wh == s;
-}
-
-// All of the node belongs to image I for the lane, and its farthest point is below cut2.
-__device__ __forceinline__ bool box_inside(const lsk::GroupQuery &Q, const float4 &lo4, const float4 &hi4,
-                                           const Axis &X, const Axis &Y, const Axis &Z, const Image &I, float cut2) {
-  float fx, fy, fz;
-  const bool in_x = far1(Q.x, lo4.x, hi4.x, X, I.x.s, fx), in_y = far1(Q.y, lo4.y, hi4.y, Y, I.y.s, fy),
-             in_z = far1(Q.z, lo4.z, hi4.z, Z, I.z.s, fz);
-  return in_x && in_y && in_z && lsk::dist2(fx, fy, fz) < cut2;
-}
-
-// The group's three axes against the root box.
-struct Frame {
-  Axis X, Y, Z;
-  float4 rlo, rhi;  // the root's box
-};
-
-__device__ __forceinline__ Frame make_frame(const lsk_tree_view &T, const float *L, const lsk::box3f &gb) {
-  const float4 *nodes = (const float4 *)T.nodes;
-  const float4 lo = nodes[2], hi = nodes[3];
-  Frame F;
-  F.rlo = make_float4(lsk::uniform_f(lo.x), lsk::uniform_f(lo.y), lsk::uniform_f(lo.z), 0.f);
-  F.rhi = make_float4(lsk::uniform_f(hi.x), lsk::uniform_f(hi.y), lsk::uniform_f(hi.z), 0.f);
-  F.X = make_axis(L[0], gb.lo.x, gb.hi.x, F.rlo.x, F.rhi.x);
-  F.Y = make_axis(L[1], gb.lo.y, gb.hi.y, F.rlo.y, F.rhi.y);
-  F.Z = make_axis(L[2], gb.lo.z, gb.hi.z, F.rlo.z, F.rhi.z);
-  return F;
-}
-
-// scan_bucket of ball_walk.h under the period: cand(pd2, the pair's wrap vector is the
-// image's, core flag (kCore), sorted position, input row (kIds), use).
-template <bool kIds, bool kCore, class Cand>
-__device__ __forceinline__ int scan_bucket_periodic(const lsk_tree_view &T, const uint32_t *perm,
-                                                    const uint8_t *core, uint32_t node, int lane,
-                                                    const lsk::GroupQuery &Q, const Frame &F, const Image &I,
-                                                    bool &use, Cand cand) {
-  const int64_t base = ((int64_t)node - ((int64_t)1 << T.depth)) * lsk::kBucket;
-  if (base >= T.n) return 0;
-  const int cnt = (int)min((int64_t)lsk::kBucket, T.n - base);
-  const int64_t pi = base + lane;
-  float px = 0.f, py = 0.f, pz = 0.f;
-  uint32_t pid = 0, pc = 0;
-  if (lane < cnt) {
-    px = T.pts[3 * pi];
-    py = T.pts[3 * pi + 1];
-    pz = T.pts[3 * pi + 2];
-    if (kCore) pc = core[pi];
-    if (kIds) pid = perm[pi];
-  }
-  for (int j = 0; j < cnt; j++) {
-    const float x = lsk::readlane_f(px, j), y = lsk::readlane_f(py, j), z = lsk::readlane_f(pz, j);
-    uint32_t c = 1, id = 0;
-    if (kCore) c = (uint32_t)__builtin_amdgcn_readlane((int)pc, j);
-    if (kIds) id = (uint32_t)__builtin_amdgcn_readlane((int)pid, j);
-    if (use) {
-      int wx, wy, wz;
-      const float dx = wrap1(Q.x - x, F.X.L, F.X.h, wx), dy = wrap1(Q.y - y, F.Y.L, F.Y.h, wy),
-                  dz = wrap1(Q.z - z, F.Z.L, F.Z.h, wz);
-      cand(lsk::dist2(dx, dy, dz), wx == I.x.s && wy == I.y.s && wz == I.z.s, c, (uint32_t)(base + j), id, use);
-    }
-  }
-  return cnt;
-}
 
 struct PerRadArgs {
   lsk_tree_view T;

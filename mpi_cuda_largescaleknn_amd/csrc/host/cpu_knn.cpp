@@ -390,6 +390,54 @@ extern "C" void lsk_cpu_radius_periodic_fill(const float *pts, int64_t n, const 
   });
 }
 
+// lsk_cpu_kth_brute under a period: the k-th smallest pdist2 among those < cut2, else cut2.
+extern "C" void lsk_cpu_kth_periodic(const float *pts, int64_t n, const float *qry, int64_t nq, int k, float cut2,
+                                     const float *period, float *out_d2, int nthreads) {
+  const vec3f *P = (const vec3f *)pts;
+  const vec3f *Q = (const vec3f *)qry;
+  parallel_for(nq, nthreads, [&](int64_t b, int64_t e) {
+    std::vector<float> d;
+    d.reserve((size_t)n);
+    for (int64_t qi = b; qi < e; qi++) {
+      d.clear();
+      for (int64_t i = 0; i < n; i++) {
+        const float v = pdist2(Q[qi], P[i], period);
+        if (v < cut2) d.push_back(v);
+      }
+      if ((int64_t)d.size() < k) {
+        out_d2[qi] = cut2;
+      } else {
+        std::nth_element(d.begin(), d.begin() + (k - 1), d.end());
+        out_d2[qi] = d[(size_t)k - 1];
+      }
+    }
+  });
+}
+
+// lsk_cpu_knn_brute under a period, the same selection and tie rule.
+extern "C" void lsk_cpu_knn_periodic(const float *pts, int64_t n, const float *qry, int64_t nq, int k, float cut2,
+                                     const float *period, int32_t *out_idx, float *out_d2, int nthreads) {
+  const vec3f *P = (const vec3f *)pts;
+  const vec3f *Q = (const vec3f *)qry;
+  parallel_for(nq, nthreads, [&](int64_t b, int64_t e) {
+    std::vector<uint64_t> d;  // d2 bits << 32 | input row, as lsk_cpu_knn_brute
+    d.reserve((size_t)n);
+    for (int64_t qi = b; qi < e; qi++) {
+      d.clear();
+      for (int64_t i = 0; i < n; i++) {
+        const float v = pdist2(Q[qi], P[i], period);
+        if (v < cut2) d.push_back(((uint64_t)lsk::fbits(v) << 32) | (uint32_t)i);
+      }
+      const size_t m = std::min<size_t>(d.size(), (size_t)k);
+      std::partial_sort(d.begin(), d.begin() + m, d.end());
+      for (size_t j = 0; j < (size_t)k; j++) {
+        out_idx[qi * k + (int64_t)j] = j < m ? (int32_t)(uint32_t)d[j] : -1;
+        out_d2[qi * k + (int64_t)j] = j < m ? lsk::bitsf((uint32_t)(d[j] >> 32)) : cut2;
+      }
+    }
+  });
+}
+
 // lsk_cpu_cluster under a period: the same definition with pdist2 for dist2.
 extern "C" void lsk_cpu_cluster_periodic(const float *pts, int64_t n, float cut2, int min_pts, const float *period,
                                          int32_t *labels, uint8_t *core, int nthreads) {

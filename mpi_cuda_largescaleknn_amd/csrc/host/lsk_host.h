@@ -117,6 +117,13 @@ void lsk_cpu_radius_periodic_fill(const float *pts, int64_t n, const float *qry,
                                   int32_t *out_idx, float *out_d2, int nthreads);
 void lsk_cpu_cluster_periodic(const float *pts, int64_t n, float cut2, int min_pts, const float *period,
                               int32_t *labels, uint8_t *core, int nthreads);
+// lsk_cpu_kth_brute / lsk_cpu_knn_brute under a period: brute force over all points with the
+// periodic squared distance above, the same selection (k-th smallest by bits among those <
+// cut2, else cut2) and the same tie rule (ascending (d² bits, row); unfilled: -1 / cut2).
+void lsk_cpu_kth_periodic(const float *pts, int64_t n, const float *qry, int64_t nq, int k, float cut2,
+                          const float *period, float *out_d2, int nthreads);
+void lsk_cpu_knn_periodic(const float *pts, int64_t n, const float *qry, int64_t nq, int k, float cut2,
+                          const float *period, int32_t *out_idx, float *out_d2, int nthreads);
 // Verification counts (= lsk_hip_count_below): counts[2j] +=#{p : dist2(q_j,p) < thr[2j]},
 // counts[2j+1] += #{p : dist2(q_j,p) < thr[2j+1]}.
 void lsk_cpu_count_below(const float *pts, int64_t n, const float *qry, const float *thr, int nq,

@@ -118,6 +118,7 @@ class LocalIndex:
                                       # keys, tree boxes and box tests use (flat_frame), or None
     bkeys: torch.Tensor | None = None  # int32 [ceil(n / 64)]: curve key of sorted point 64 b
                                        # (bucket_keys: built by the first foreign query)
+    line: bool = False       # sorted by line_keys (a LineAxis frame), not by the curve of `box`
 
     @property
     def device(self) -> torch.device:
@@ -301,9 +302,10 @@ def build_index(points: torch.Tensor, box: torch.Tensor | None = None,
     (refine_heavy_cells; under host_sync_free() not even that)."""
     points = points.contiguous()
     n = points.shape[0]
+    line = False
     if isinstance(frame, LineAxis):  # a line: its own frame, keys along its axis, no grid
         if keys is None and K.is_gpu(points) and n >= 2:
-            keys, grid = (line_keys(points, frame.a), None), False
+            keys, grid, line = (line_keys(points, frame.a), None), False, True
         frame = None
     if frame is not None and K.is_gpu(points) and keys is None and box is None and n >= 2:
         return _build_rotated(points, frame)
@@ -328,7 +330,7 @@ def build_index(points: torch.Tensor, box: torch.Tensor | None = None,
     # (a refinement reorders over-full cells: the fused gather's order is then stale)
     pts = spts if spts is not None and perm is sorted_perm else K.gather3(points, perm, pad=K.PAD_POINTS)
     nodes, qnodes, depth = K.build_tree(pts, n)
-    index = LocalIndex(n, pts, perm, nodes, qnodes, depth, box)
+    index = LocalIndex(n, pts, perm, nodes, qnodes, depth, box, line=line)
     if grid:
         index.grid = build_grid(index, skeys, density_n, grid_level,
                                 counts=census[0] if census is not None else None, gated=grid_gated)
@@ -815,9 +817,14 @@ def verify_captured_failures(clear: bool = False) -> int:
 
 
 def knn_distances(points: torch.Tensor, k: int, max_radius: float = math.inf,
-                  stats: KnnStats | None = None) -> torch.Tensor:
+                  stats: KnnStats | None = None, period=None) -> torch.Tensor:
     """Distance from every point to its k-th nearest neighbour among `points`
-    (itself counted), in input order — the single-rank reference output."""
+    (itself counted), in input order — the single-rank reference output. Open-box only: a
+    `period` raises ValueError ("not supported"; knn_query_distances(points, points, ...) takes
+    one)."""
+    if period is not None:
+        raise ValueError("knn_distances: a period is not supported (knn_query_distances(points, points, k, "
+                         "period=...) gives the periodic k-th distances)")
     cfg = KnnConfig(k=k, max_radius=max_radius)
     probe = FrameProbe(points, k)
     if FRAME_EARLY:  # the probe read before the build (a short host wait, no wasted build)
@@ -881,28 +888,116 @@ def _cutoff_distances(shape: tuple, cut2: float, device: torch.device) -> torch.
 
 
 def query_points(index: LocalIndex, queries: torch.Tensor, cfg: KnnConfig, stats: KnnStats | None = None,
-                 out: torch.Tensor | None = None, qstatus: torch.Tensor | None = None) -> torch.Tensor:
+                 out: torch.Tensor | None = None, qstatus: torch.Tensor | None = None, period=None,
+                 max_pairs: int = 1 << 28, flagged: torch.Tensor | None = None) -> torch.Tensor:
     """Distance from every row of `queries` (float32 [nq, 3] on the index's device) to its
     k-th nearest point of `index` (build_index(points, grid=True)), in query order. Only the
     index's points are candidates: a query that coincides with one finds it at distance 0,
     and no query is a candidate for another. The cutoff and k > n behave as in `query`.
     An index built in a rotated frame serves its own points only. `qstatus` (int32 [nq],
-    debugging): the kernels' per-query status words, in curve-sorted query order."""
+    debugging): the kernels' per-query status words, in curve-sorted query order.
+    period: one value L or (Lx, Ly, Lz), each > 0, inf = open axis: the distance of a pair is
+    the minimum image of its difference (radius_counts states the arithmetic), with no bound on
+    the radius: the k-th smallest periodic squared distance by its bits among those below the
+    cutoff. Only queries whose open-box ball reaches a face pay for it: they run a periodic
+    radius search of at most `max_pairs` pairs at a time (a single query with more raises
+    ValueError). `stats` also receives periodic_flagged, periodic_pairs and radius_images;
+    `flagged` (bool [nq], tests) the queries that took the periodic passes."""
+    per = _knn_period("query_points", index, period)
     queries = _check_foreign("query_points", index, queries)
     nq, n = queries.shape[0], index.n
     if out is None:
         out = torch.empty(nq, dtype=torch.float32, device=index.device)
+    if flagged is not None:
+        flagged.fill_(False)
     if nq == 0:
         return out
     if not K.is_gpu(index.pts):
-        out.copy_(K.finalize_distances(K.kth_cpu(index.pts[:n], queries, cfg.k, cfg.cut2)))
+        d2 = K.kth_cpu(index.pts[:n], queries, cfg.k, cfg.cut2) if per is None else \
+            K.kth_periodic_cpu(index.pts[:n], queries, cfg.k, cfg.cut2, per)
+        out.copy_(K.finalize_distances(d2))
         KERNELS_USED.add("cpu")
         return out
     if n == 0:  # no candidate at all: every answer is the cutoff
         out.copy_(_cutoff_distances((nq,), cfg.cut2, index.device))
         return out
-    _foreign_kth(index, queries, cfg, stats, out, qstatus)
+    if per is None or cfg.k > n:  # (k > n: the cutoff under any distance)
+        _foreign_kth(index, queries, cfg, stats, out, qstatus)
+        return out
+    qsorted, qperm, d2 = _foreign_kth(index, queries, cfg, stats, out, qstatus, want_d2=True)
+    _periodic_knn(index, per, cfg, qsorted, qperm, d2, out, None, None, stats, max_pairs, flagged)
     return out
+
+
+def _knn_period(what: str, index: LocalIndex | None, period) -> tuple | None:
+    """The checked period of a k-NN query (None: open box, also when every axis is open);
+    ValueError for a bad period, or a finite one with an index built in a rotated frame or
+    sorted by line keys."""
+    if period is None:
+        return None
+    per = K.check_period(what, period)
+    if all(math.isinf(v) for v in per):
+        return None
+    if index is not None and (index.qrot is not None or index.line):
+        raise ValueError(f"{what}: a period is not supported for an index built in a rotated frame or sorted "
+                         "by line keys")
+    return per
+
+
+# the device error word of the last periodic k-NN pass (tests: always 0)
+LAST_PERIODIC_KNN_ERRORS = [0]
+
+
+def _periodic_knn(index: LocalIndex, per: tuple, cfg: KnnConfig, qsorted: torch.Tensor, qperm: torch.Tensor,
+                  d2: torch.Tensor, out: torch.Tensor, out_idx: torch.Tensor | None, out_dist: torch.Tensor | None,
+                  stats: KnnStats | None, max_pairs: int, flagged: torch.Tensor | None) -> None:
+    """Turns the open-box results of _foreign_kth (and of the collect pass) into the periodic
+    ones (knn_periodic.hip): the open-box k-th squared distance d2 bounds the periodic one, so
+    only queries whose ball of that radius reaches a non-zero image of the root box are flagged;
+    they run a periodic radius search with that bound, in slices of at most max_pairs pairs,
+    and the first k of each sorted row overwrite their entries of out / out_idx / out_dist."""
+    nq = d2.shape[0]
+    tree = index.tree()
+    cutq, flags = K.pknn_flag_gpu(tree, qsorted, nq, d2, cfg.cut2, per)
+    KERNELS_USED.add("knn_periodic")
+    qlist = torch.nonzero(flags).view(-1).int()  # (host read: the list's length)
+    m = qlist.numel()
+    if flagged is not None:
+        flagged[qperm[qlist.long()].long()] = True
+    raw = torch.zeros(K.RADIUS_PERIODIC_STATS, dtype=torch.int64, device=index.device) if stats is not None else None
+    pairs = 0
+    LAST_PERIODIC_KNN_ERRORS[0] = 0
+    if m:
+        counts = K.pknn_count_gpu(tree, qsorted, nq, qlist, cutq, per, stats=raw)
+        cum = torch.zeros(m + 1, dtype=torch.int64, device=index.device)
+        torch.cumsum(counts, 0, dtype=torch.int64, out=cum[1:])
+        hcum = cum.cpu()  # (host read: decides the slices)
+        pairs = int(hcum[m])
+        hcounts = hcum[1:] - hcum[:-1]
+        if int(hcounts.max()) > max_pairs:
+            raise ValueError(f"periodic k-NN: a query has {int(hcounts.max())} points within its open-box k-th "
+                             f"distance, more than max_pairs = {max_pairs}; raise max_pairs")
+        err = torch.zeros(1, dtype=torch.int32, device=index.device)
+        a = 0
+        while a < m:
+            # the longest run of rows from a within max_pairs pairs (at least one: checked above)
+            b = int(torch.searchsorted(hcum, hcum[a] + max_pairs, right=True)) - 1
+            b = max(a + 1, min(b, m))
+            offsets = (cum[a:b + 1] - cum[a]).contiguous()
+            K.pknn_rows_gpu(tree, index.perm, qsorted, nq, qlist[a:b].contiguous(), cutq, per, offsets,
+                            int(hcum[b] - hcum[a]), int(hcounts[a:b].max()), qperm, d2, cfg.cut2, cfg.k, out,
+                            out_idx, out_dist, err)
+            a = b
+        LAST_PERIODIC_KNN_ERRORS[0] = int(err.item()) & 0xFFFFFFFF
+    if stats is not None:
+        for nm, v in zip(_RADIUS_PERIODIC_STATS, raw.cpu().tolist()):
+            stats.counters[nm] = stats.counters.get(nm, 0) + int(v)
+        stats.counters["periodic_flagged"] = stats.counters.get("periodic_flagged", 0) + m
+        stats.counters["periodic_pairs"] = stats.counters.get("periodic_pairs", 0) + pairs
+    if LAST_PERIODIC_KNN_ERRORS[0]:
+        raise NativeError(f"periodic k-NN: {LAST_PERIODIC_KNN_ERRORS[0]} rows were not filled to their count or held "
+                          "fewer than k points within the open-box k-th distance (a bug: that distance bounds "
+                          "the periodic one)")
 
 
 def _foreign_kth(index: LocalIndex, queries: torch.Tensor, cfg: KnnConfig, stats: KnnStats | None,
@@ -944,28 +1039,37 @@ def _foreign_kth(index: LocalIndex, queries: torch.Tensor, cfg: KnnConfig, stats
 
 
 def knn_query_distances(points: torch.Tensor, queries: torch.Tensor, k: int, max_radius: float = math.inf,
-                        stats: KnnStats | None = None) -> torch.Tensor:
+                        stats: KnnStats | None = None, period=None, max_pairs: int = 1 << 28,
+                        flagged: torch.Tensor | None = None) -> torch.Tensor:
     """Distance from every row of `queries` to its k-th nearest neighbour among `points`
     (both float32 [*, 3] on one device), in query order. The index is built in the points'
-    own frame (no rotated frame, no line keys), so queries off a planar set's plane work."""
+    own frame (no rotated frame, no line keys), so queries off a planar set's plane work.
+    period / max_pairs / flagged: see query_points."""
     if points.device != queries.device:
         raise ValueError(f"knn_query_distances: points on {points.device}, queries on {queries.device}")
+    _knn_period("knn_query_distances", None, period)
     cfg = KnnConfig(k=k, max_radius=max_radius)
     if points.shape[0] == 0:  # nothing to index: every answer is the cutoff
+        if flagged is not None:
+            flagged.fill_(False)
         return _cutoff_distances((queries.shape[0],), cfg.cut2, queries.device)
     index = build_index(points, grid=True)
-    return query_points(index, queries, cfg, stats=stats)
+    return query_points(index, queries, cfg, stats=stats, period=period, max_pairs=max_pairs, flagged=flagged)
 
 
 def query_neighbors(index: LocalIndex, queries: torch.Tensor, cfg: KnnConfig, stats: KnnStats | None = None,
-                    out_idx: torch.Tensor | None = None, out_dist: torch.Tensor | None = None) -> tuple:
+                    out_idx: torch.Tensor | None = None, out_dist: torch.Tensor | None = None, period=None,
+                    max_pairs: int = 1 << 28, flagged: torch.Tensor | None = None) -> tuple:
     """Neighbour lists: (idx int32 [nq, k], dist float32 [nq, k]) in query order — for every
     row of `queries` the ids (rows of the indexed array) and distances of its k nearest
     points of `index` within the cutoff, ascending by (distance, row): ties at any distance,
     the k-th included, go to the lowest rows, whatever the index's internal order. Unfilled
     slots (fewer than k points qualify) hold -1 and the value the k-th-distance API returns
     there; dist[:, k - 1] is query_points' output bit for bit. Same inputs and limits as
-    query_points, and k <= K.NEIGHBORS_MAX_K."""
+    query_points, and k <= K.NEIGHBORS_MAX_K. period / max_pairs / flagged as in query_points:
+    the lists are the first k of { (pd2, row) : pd2 < cut2 } with pd2 the periodic squared
+    distance, in the same order and with the same tie rule."""
+    per = _knn_period("query_neighbors", index, period)
     queries = _check_foreign("query_neighbors", index, queries)
     k = cfg.k
     if k < 1:
@@ -981,11 +1085,14 @@ def query_neighbors(index: LocalIndex, queries: torch.Tensor, cfg: KnnConfig, st
     for t, dt in ((out_idx, torch.int32), (out_dist, torch.float32)):
         if t.shape != (nq, k) or t.dtype != dt or not t.is_contiguous() or t.device != index.device:
             raise ValueError("query_neighbors: out_idx int32 / out_dist float32, contiguous [nq, k] on the index's device")
+    if flagged is not None:
+        flagged.fill_(False)
     if nq == 0:
         return out_idx, out_dist
     if not K.is_gpu(index.pts):
         # (ids are rows of the input array: the lists are taken over the points in input order)
-        idx, d2 = K.knn_cpu(_input_order(index), queries, k, cfg.cut2)
+        idx, d2 = K.knn_cpu(_input_order(index), queries, k, cfg.cut2) if per is None else \
+            K.knn_periodic_cpu(_input_order(index), queries, k, cfg.cut2, per)
         out_idx.copy_(idx)
         out_dist.copy_(K.finalize_distances(d2.view(-1)).view(nq, k))
         KERNELS_USED.add("cpu")
@@ -1001,6 +1108,8 @@ def query_neighbors(index: LocalIndex, queries: torch.Tensor, cfg: KnnConfig, st
     if LAST_NEIGHBOR_ERRORS[0]:
         raise NativeError(f"query_neighbors: {LAST_NEIGHBOR_ERRORS[0]} queries were handed a k-th distance that is "
                           "not their k-th value (a bug in the k-th pass or the collect pass)")
+    if per is not None:  # (k > n included: the unfilled lists hold periodic distances too)
+        _periodic_knn(index, per, cfg, qsorted, qperm, d2, kth, out_idx, out_dist, stats, max_pairs, flagged)
     return out_idx, out_dist
 
 
@@ -1009,29 +1118,36 @@ LAST_NEIGHBOR_ERRORS = [0]
 
 
 def knn_query_neighbors(points: torch.Tensor, queries: torch.Tensor, k: int, max_radius: float = math.inf,
-                        stats: KnnStats | None = None) -> tuple:
+                        stats: KnnStats | None = None, period=None, max_pairs: int = 1 << 28,
+                        flagged: torch.Tensor | None = None) -> tuple:
     """(idx int32 [nq, k], dist float32 [nq, k]): ids and distances of the k nearest rows of
     `points` for every row of `queries` (both float32 [*, 3] on one device), see
-    query_neighbors. The index is built once, in the points' own frame."""
+    query_neighbors (period / max_pairs / flagged too). The index is built once, in the
+    points' own frame."""
     if points.device != queries.device:
         raise ValueError(f"knn_query_neighbors: points on {points.device}, queries on {queries.device}")
+    _knn_period("knn_query_neighbors", None, period)
     cfg = KnnConfig(k=k, max_radius=max_radius)
     if k > K.NEIGHBORS_MAX_K:
         raise ValueError(f"knn_query_neighbors: k = {k} exceeds {K.NEIGHBORS_MAX_K} neighbours per query; "
                          "knn_query_distances gives the k-th distance for any k")
     if points.shape[0] == 0:  # nothing to index: every slot is unfilled
         nq = queries.shape[0]
+        if flagged is not None:
+            flagged.fill_(False)
         return (torch.full((nq, k), -1, dtype=torch.int32, device=queries.device),
                 _cutoff_distances((nq, k), cfg.cut2, queries.device))
     index = build_index(points, grid=True)
-    return query_neighbors(index, queries, cfg, stats=stats)
+    return query_neighbors(index, queries, cfg, stats=stats, period=period, max_pairs=max_pairs, flagged=flagged)
 
 
 def knn_neighbors(points: torch.Tensor, k: int, max_radius: float = math.inf,
-                  stats: KnnStats | None = None) -> tuple:
+                  stats: KnnStats | None = None, period=None, max_pairs: int = 1 << 28,
+                  flagged: torch.Tensor | None = None) -> tuple:
     """knn_query_neighbors with the points as their own queries: every point's list starts
     with a point at distance 0 (itself, or the lowest row among its exact copies)."""
-    return knn_query_neighbors(points, points, k, max_radius, stats=stats)
+    return knn_query_neighbors(points, points, k, max_radius, stats=stats, period=period, max_pairs=max_pairs,
+                               flagged=flagged)
 
 
 # ------------------------------------------------------------------ fixed-radius search

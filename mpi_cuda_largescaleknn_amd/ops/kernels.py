@@ -1067,6 +1067,108 @@ def cluster_periodic_gpu(tree: tuple, perm: torch.Tensor, core_sorted: torch.Ten
     return labels, err
 
 
+# --------------------------------------------------------------------------- periodic k-NN
+def kth_periodic_cpu(points: torch.Tensor, queries: torch.Tensor, k: int, cut2: float, period) -> torch.Tensor:
+    """CPU oracle (brute force): kth_cpu with the periodic squared distance of
+    radius_periodic_count_cpu: float32 [nq], per query the k-th smallest pd2 among those < cut2,
+    cut2 when fewer than k qualify."""
+    if k < 1:
+        raise ValueError("kth_periodic_cpu: k must be at least 1")
+    per = check_period("kth_periodic_cpu", period)
+    pts = points.contiguous().float().cpu()
+    q = queries.contiguous().float().cpu()
+    out = torch.empty(q.shape[0], dtype=torch.float32)
+    _native.host().lsk_cpu_kth_periodic(_ptr(pts), pts.shape[0], _ptr(q), q.shape[0], int(k), C.c_float(cut2),
+                                        _period_c(per), _ptr(out), _nthreads())
+    return out
+
+
+def knn_periodic_cpu(points: torch.Tensor, queries: torch.Tensor, k: int, cut2: float,
+                     period) -> tuple[torch.Tensor, torch.Tensor]:
+    """CPU oracle of the periodic neighbour lists (brute force): knn_cpu with the periodic squared
+    distance, the same order, tie rule and unfilled slots. d2[:, k - 1] equals kth_periodic_cpu."""
+    if k < 1:
+        raise ValueError("knn_periodic_cpu: k must be at least 1")
+    per = check_period("knn_periodic_cpu", period)
+    pts = points.contiguous().float().cpu()
+    q = queries.contiguous().float().cpu()
+    idx = torch.empty((q.shape[0], k), dtype=torch.int32)
+    d2 = torch.empty((q.shape[0], k), dtype=torch.float32)
+    _native.host().lsk_cpu_knn_periodic(_ptr(pts), pts.shape[0], _ptr(q), q.shape[0], int(k), C.c_float(cut2),
+                                        _period_c(per), _ptr(idx), _ptr(d2), _nthreads())
+    return idx, d2
+
+
+def _pknn_view(what: str, tree: tuple, qsorted: torch.Tensor, nq: int, **arrays) -> TreeView:
+    """The view of `tree` for the periodic k-NN passes; arrays: name = (tensor, dtype, least size)."""
+    pts, nodes, qnodes, n, depth = tree
+    if qsorted.shape[0] < nq or qsorted.device != pts.device:
+        raise ValueError(f"{what}: qsorted [>= nq, 3] on the tree's device")
+    for name, (t, dt, cnt) in arrays.items():
+        if t.dtype != dt or t.numel() < cnt or not t.is_contiguous() or t.device != pts.device:
+            raise ValueError(f"{what}: {name} must be {dt} [>= {cnt}], contiguous, on the tree's device")
+    return TreeView(_ptr(pts), _ptr(nodes), _ptr(qnodes), n, depth, 0)
+
+
+def pknn_flag_gpu(tree: tuple, qsorted: torch.Tensor, nq: int, d2: torch.Tensor, cut2: float,
+                  period: tuple[float, float, float]) -> tuple[torch.Tensor, torch.Tensor]:
+    """The flag pass of the periodic k-NN (knn_periodic.hip): (cutq float32 [nq], flags int32 [nq]),
+    both in the order of the curve-sorted queries, from their open-box k-th squared distances d2.
+    cutq: the closed bound d2 as a strict cutoff; flags: 1 where a wrapped point may lie below it."""
+    tv = _pknn_view("pknn_flag_gpu", tree, qsorted, nq, d2=(d2, torch.float32, nq))
+    dev = tree[0].device
+    cutq = torch.empty(nq, dtype=torch.float32, device=dev)
+    flags = torch.empty(nq, dtype=torch.int32, device=dev)
+    check(_native.hip().lsk_hip_pknn_flag(C.byref(tv), _ptr(qsorted), _ptr(d2), int(nq), C.c_float(cut2),
+                                          _period_c(period), _ptr(cutq), _ptr(flags), _stream(tree[0])), "pknn_flag")
+    return cutq, flags
+
+
+def pknn_count_gpu(tree: tuple, qsorted: torch.Tensor, nq: int, qlist: torch.Tensor, cutq: torch.Tensor,
+                   period: tuple[float, float, float], stats: torch.Tensor | None = None) -> torch.Tensor:
+    """The count pass over the flagged list: int32 [m], per entry of qlist (int32, ascending
+    positions of the curve-sorted queries) the number of points with pd2 < cutq[entry]. stats:
+    optional zeroed int64 [RADIUS_PERIODIC_STATS]."""
+    m = qlist.numel()
+    tv = _pknn_view("pknn_count_gpu", tree, qsorted, nq, qlist=(qlist, torch.int32, m), cutq=(cutq, torch.float32, nq))
+    counts = torch.empty(m, dtype=torch.int32, device=tree[0].device)
+    check(_native.hip().lsk_hip_pknn_count(C.byref(tv), _ptr(qsorted), _ptr(qlist), int(m), _ptr(cutq),
+                                           _period_c(period), _ptr(counts), _ptr(stats), _stream(tree[0])),
+          "pknn_count")
+    return counts
+
+
+def pknn_rows_gpu(tree: tuple, perm: torch.Tensor, qsorted: torch.Tensor, nq: int, qlist: torch.Tensor,
+                  cutq: torch.Tensor, period: tuple[float, float, float], offsets: torch.Tensor, total: int,
+                  longest: int, qperm: torch.Tensor, d2: torch.Tensor, cut2: float, k: int, out: torch.Tensor,
+                  out_idx: torch.Tensor | None, out_dist: torch.Tensor | None, err: torch.Tensor) -> None:
+    """Fill, sort and take for one slice of the flagged list: the rows `offsets` (int64 [m + 1],
+    from pknn_count_gpu's counts of this slice; total = offsets[m], longest >= the longest row)
+    are filled, sorted by lsk_hip_radius_sort, and their first k overwrite out[qperm[q]] (and
+    rows qperm[q] of out_idx / out_dist [nq, k], when given) of the slice's queries. err: the
+    device error word (int32 [1], accumulated over the slices)."""
+    m = qlist.numel()
+    arrays = dict(qlist=(qlist, torch.int32, m), cutq=(cutq, torch.float32, nq), perm=(perm, torch.int32, tree[3]),
+                  offsets=(offsets, torch.int64, m + 1), qperm=(qperm, torch.int32, nq), d2=(d2, torch.float32, nq),
+                  out=(out, torch.float32, nq), err=(err, torch.int32, 1))
+    if out_idx is not None:
+        arrays.update(out_idx=(out_idx, torch.int32, nq * k), out_dist=(out_dist, torch.float32, nq * k))
+    tv = _pknn_view("pknn_rows_gpu", tree, qsorted, nq, **arrays)
+    if offsets.numel() != m + 1 or k < 1:
+        raise ValueError("pknn_rows_gpu: offsets must be [m + 1] and k >= 1")
+    dev = tree[0].device
+    lib, st = _native.hip(), _stream(tree[0])
+    idx = torch.empty(total, dtype=torch.int32, device=dev)
+    dist = torch.empty(total, dtype=torch.float32, device=dev)
+    check(lib.lsk_hip_pknn_fill(C.byref(tv), _ptr(perm), _ptr(qsorted), _ptr(qlist), int(m), _ptr(cutq),
+                                _period_c(period), _ptr(offsets), _ptr(idx), _ptr(dist), _ptr(err), st), "pknn_fill")
+    check(lib.lsk_hip_radius_sort(_ptr(offsets), int(m), int(total), int(longest), _ptr(idx), _ptr(dist), 1, st),
+          "radius_sort")
+    check(lib.lsk_hip_pknn_take(_ptr(qlist), int(m), _ptr(offsets), _ptr(idx), _ptr(dist), _ptr(qperm), _ptr(d2),
+                                C.c_float(cut2), int(k), _ptr(out), _ptr(out_idx), _ptr(out_dist), _ptr(err), st),
+          "pknn_take")
+
+
 # --------------------------------------------------------------------------- halo
 UB_MAX_W = 8  # tree.hip kUbMaxW: beyond it the box-pair bound
 

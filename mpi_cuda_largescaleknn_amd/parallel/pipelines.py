@@ -792,11 +792,18 @@ def local_query(index: E.LocalIndex, hint2, cfg: E.KnnConfig, info: RunInfo | No
     return out
 
 
+def _no_period(what: str, period) -> None:
+    if period is not None:
+        raise ValueError(f"{what}: a period is not supported by the multi-rank pipelines (the single-rank "
+                         "knn_query_distances / knn_query_neighbors take one)")
+
+
 def unordered_knn(points: torch.Tensor, comm: Comm, cfg: E.KnnConfig, info: RunInfo | None = None,
                   n_total: int | None = None, out: torch.Tensor | None = None,
-                  direct: bool | None = None) -> torch.Tensor:
+                  direct: bool | None = None, period=None) -> torch.Tensor:
     """k-th-NN distance of every local point (input order) for a globally unordered set
-    block-partitioned over ranks (reference unorderedData variant).
+    block-partitioned over ranks (reference unorderedData variant). Open-box only: a `period`
+    raises ValueError ("not supported").
 
     `points` may live in (pinned) host memory: on several ranks the redistribution then
     streams them to the device in chunks overlapped with the exchange
@@ -805,6 +812,7 @@ def unordered_knn(points: torch.Tensor, comm: Comm, cfg: E.KnnConfig, info: RunI
     `out` is written by the k-NN kernel over PCIe while it runs, or through a device buffer
     and one copy (`direct`, see query_into: by default the copy when the cell grid is
     built, the direct writes for the bucket-tree kernel)."""
+    _no_period("unordered_knn", period)
     info = info or RunInfo(PhaseTimer(False, comm.device))
     info.timer.start()
     points = points.contiguous()
@@ -913,9 +921,10 @@ IMBALANCE_LIMIT = 1.2  # --balance auto: rebalance when max/mean points per rank
 
 def prepartitioned_knn(points: torch.Tensor, comm: Comm, cfg: E.KnnConfig,
                        info: RunInfo | None = None, out: torch.Tensor | None = None,
-                       balance: str = "auto", direct: bool | None = None) -> torch.Tensor:
+                       balance: str = "auto", direct: bool | None = None, period=None) -> torch.Tensor:
     """k-th-NN distance of every local point (input order) when each rank holds one
-    (spatially coherent) input file (reference prePartitionedData variant). `out` as in
+    (spatially coherent) input file (reference prePartitionedData variant). Open-box only: a
+    `period` raises ValueError ("not supported"). `out` as in
     unordered_knn (on one rank a pinned host tensor is written by the kernel directly).
 
     Skewed file sets: the reference serves a hot rank's whole shard to
@@ -924,6 +933,7 @@ def prepartitioned_knn(points: torch.Tensor, comm: Comm, cfg: E.KnnConfig,
     the files go through the unordered pipeline instead (count-balanced spatial
     redistribution, halo, return): every rank owns ~N/P points and each file's results
     still come back in its own order."""
+    _no_period("prepartitioned_knn", period)
     if balance not in ("auto", "on", "off"):
         raise ValueError(f"balance must be auto, on or off, not {balance!r}")
     info = info or RunInfo(PhaseTimer(False, points.device))

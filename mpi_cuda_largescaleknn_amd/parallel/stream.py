@@ -72,7 +72,9 @@ class SetStream:
     """
 
     def __init__(self, comm: Comm, cfg: E.KnnConfig, direct_out: bool = True,
-                 variant: str = "unordered", pre_keys: bool | None = None):
+                 variant: str = "unordered", pre_keys: bool | None = None, period=None):
+        if period is not None:
+            raise ValueError("SetStream: a period is not supported (the streamed sets are open-box)")
         if variant not in ("unordered", "prepartitioned"):
             raise ValueError(f"SetStream: variant must be unordered or prepartitioned, not {variant!r}")
         self.comm = comm

@@ -26,6 +26,7 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
+from mpi_cuda_largescaleknn_amd.apps.radius import add_period_option  # noqa: E402
 from mpi_cuda_largescaleknn_amd.models import knn_engine as E  # noqa: E402
 from mpi_cuda_largescaleknn_amd.ops import kernels as K  # noqa: E402
 
@@ -49,7 +50,9 @@ def main() -> int:
     ap.add_argument("--k", type=int, default=100)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    add_period_option(ap)  # the cross query (cross_total_s) under the period, checked against the periodic oracle
     a = ap.parse_args()
+    per = {} if a.period is None else {"period": a.period}  # (none: the calls without the keyword)
     n, nq, k = int(a.points), int(a.queries), a.k
     dev = torch.device("cuda", 0)
     p = torch.rand((n, 3), generator=torch.Generator(device=dev).manual_seed(1), device=dev)
@@ -78,13 +81,17 @@ def main() -> int:
     for name, idx in (("grid", index), ("rows", rows_index)):
         fails[name] = launch(idx, prepared)
         t_query[name] = timed(lambda idx=idx: launch(idx, prepared), a.steps, a.warmup)
-    t_cross = timed(lambda: E.query_points(index, q, cfg, out=out), a.steps, a.warmup)
+    t_cross = timed(lambda: E.query_points(index, q, cfg, out=out, **per), a.steps, a.warmup)
     used = E.kernels_used()
 
     # correctness of what was timed: sampled queries against brute force over all points
-    got = E.query_points(index, q, cfg).cpu()
+    stats = E.KnnStats()
+    got = E.query_points(index, q, cfg, stats=stats, **per).cpu()
     smp = torch.randint(0, nq, (256,), generator=torch.Generator().manual_seed(3))
-    ref = K.finalize_distances(K.kth_cpu(p.cpu(), q[smp.to(dev)].cpu(), k, cfg.cut2, method="brute"))
+    if per:
+        ref = K.finalize_distances(K.kth_periodic_cpu(p.cpu(), q[smp.to(dev)].cpu(), k, cfg.cut2, per["period"]))
+    else:
+        ref = K.finalize_distances(K.kth_cpu(p.cpu(), q[smp.to(dev)].cpu(), k, cfg.cut2, method="brute"))
     exact = int((got[smp] == ref).sum())
 
     t_self = timed(lambda: E.knn_distances(p, k), a.steps, a.warmup)
@@ -99,6 +106,12 @@ def main() -> int:
         "self_total_s": t_self, "self_Mpts_per_s": n / t_self / 1e6, "self_query_only_s": t_self_query,
         "fallback_queries": fails, "kernels_used": used, "sampled_exact": f"{exact}/256",
     }
+    if per:
+        c = stats.counters
+        rec.update(period=list(per["period"]), periodic_flagged=c.get("periodic_flagged", 0),
+                   periodic_pairs=c.get("periodic_pairs", 0), radius_images=c.get("radius_images", 0),
+                   flagged_share=c.get("periodic_flagged", 0) / nq,
+                   pairs_per_flagged=c.get("periodic_pairs", 0) / max(c.get("periodic_flagged", 0), 1))
     print(json.dumps(rec), flush=True)
     return 0 if exact == 256 else 1
 

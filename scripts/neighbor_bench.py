@@ -25,6 +25,7 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
+from mpi_cuda_largescaleknn_amd.apps.radius import add_period_option  # noqa: E402
 from mpi_cuda_largescaleknn_amd.models import knn_engine as E  # noqa: E402
 from mpi_cuda_largescaleknn_amd.ops import kernels as K  # noqa: E402
 
@@ -41,7 +42,7 @@ def timed(fn, steps: int, warmup: int) -> float:
     return statistics.median(ts)
 
 
-def one(n: int, nq: int, k: int, steps: int, warmup: int) -> bool:
+def one(n: int, nq: int, k: int, steps: int, warmup: int, per: dict) -> bool:
     dev = torch.device("cuda", 0)
     p = torch.rand((n, 3), generator=torch.Generator(device=dev).manual_seed(1), device=dev)
     q = torch.rand((nq, 3), generator=torch.Generator(device=dev).manual_seed(2), device=dev)
@@ -52,8 +53,12 @@ def one(n: int, nq: int, k: int, steps: int, warmup: int) -> bool:
     idx = torch.empty((nq, k), dtype=torch.int32, device=dev)
     dist = torch.empty((nq, k), dtype=torch.float32, device=dev)
 
-    t_kth = timed(lambda: E.query_points(index, q, cfg, out=kth), steps, warmup)
-    t_lists = timed(lambda: E.query_neighbors(index, q, cfg, out_idx=idx, out_dist=dist), steps, warmup)
+    t_kth = timed(lambda: E.query_points(index, q, cfg, out=kth, **per), steps, warmup)
+    t_lists = timed(lambda: E.query_neighbors(index, q, cfg, out_idx=idx, out_dist=dist, **per), steps, warmup)
+    # what was timed, before the open-box collect pass below overwrites it
+    smp = torch.randint(0, nq, (128,), generator=torch.Generator().manual_seed(3))
+    got_i, got_d = idx[smp.to(dev)].cpu(), dist[smp.to(dev)].cpu()
+    same_kth = bool(torch.equal(dist[:, k - 1], kth))
     qsorted, qperm, d2 = E._foreign_kth(index, q, cfg, None, kth, want_d2=True)
 
     def collect():
@@ -63,17 +68,25 @@ def one(n: int, nq: int, k: int, steps: int, warmup: int) -> bool:
     assert collect() == 0
     t_collect = timed(collect, steps, warmup)
 
-    smp = torch.randint(0, nq, (128,), generator=torch.Generator().manual_seed(3))
-    ref_i, ref_d2 = K.knn_cpu(p.cpu(), q[smp.to(dev)].cpu(), k, cfg.cut2)
+    if per:
+        ref_i, ref_d2 = K.knn_periodic_cpu(p.cpu(), q[smp.to(dev)].cpu(), k, cfg.cut2, per["period"])
+    else:
+        ref_i, ref_d2 = K.knn_cpu(p.cpu(), q[smp.to(dev)].cpu(), k, cfg.cut2)
     ref_d = K.finalize_distances(ref_d2.view(-1)).view(-1, k)
-    exact = int(((idx[smp.to(dev)].cpu() == ref_i) & (dist[smp.to(dev)].cpu() == ref_d)).all(dim=1).sum())
-    same_kth = bool(torch.equal(dist[:, k - 1], kth))
+    exact = int(((got_i == ref_i) & (got_d == ref_d)).all(dim=1).sum())
     rec = {
         "points": n, "queries": nq, "k": k, "steps": steps, "warmup": warmup,
         "output_GB": nq * k * 8 / 1e9, "kth_s": t_kth, "lists_s": t_lists, "collect_sort_s": t_collect,
         "lists_over_kth": t_lists / t_kth, "lists_Mqueries_per_s": nq / t_lists / 1e6,
         "kth_Mqueries_per_s": nq / t_kth / 1e6, "sampled_exact": f"{exact}/128", "last_column_is_kth": same_kth,
     }
+    if per:
+        stats = E.KnnStats()
+        E.query_points(index, q, cfg, out=kth, stats=stats, **per)
+        c = stats.counters
+        rec.update(period=list(per["period"]), periodic_flagged=c["periodic_flagged"], periodic_pairs=c["periodic_pairs"],
+                   radius_images=c["radius_images"], flagged_share=c["periodic_flagged"] / nq,
+                   pairs_per_flagged=c["periodic_pairs"] / max(c["periodic_flagged"], 1))
     print(json.dumps(rec), flush=True)
     return exact == 128 and same_kth
 
@@ -83,11 +96,13 @@ def main() -> int:
     ap.add_argument("--shapes", default="2e7:2e7:16,2e7:4e6:100", help="points:queries:k, comma separated")
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    add_period_option(ap)  # kth_s and lists_s under the period, checked against the periodic oracle
     a = ap.parse_args()
+    per = {} if a.period is None else {"period": a.period}  # (none: the calls without the keyword)
     ok = True
     for shape in a.shapes.split(","):
         n, nq, k = shape.split(":")
-        ok = one(int(float(n)), int(float(nq)), int(k), a.steps, a.warmup) and ok
+        ok = one(int(float(n)), int(float(nq)), int(k), a.steps, a.warmup, per) and ok
         torch.cuda.empty_cache()
     return 0 if ok else 1
 
