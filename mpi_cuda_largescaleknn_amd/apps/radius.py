@@ -3,6 +3,8 @@
     hipKNN_radius <points.float3> <queries.float3> (-r <radius> | --radii FILE | --point-radii FILE) [--squared]
                   -o <PREFIX> [--counts-only] [--unsorted] [--chunk N] [--max-pairs M]
                   [--period L | Lx,Ly,Lz] [--device auto|cuda|cpu] [--stats f.json] [-v]
+    hipKNN_radius <points.float3> <queries.float3> --profile R1,R2,... [--squared] -o <PREFIX> [--pairs-only]
+                  [--chunk N] [--period L | Lx,Ly,Lz] [--device auto|cuda|cpu] [--stats f.json] [-v]
 
 For every row of the query file, the points of the point file with dist2 < radius² (float32
 product, strict: the comparison of the -r cutoff of the k-NN tools), however many there
@@ -17,6 +19,12 @@ row ascending by (distance, row) unless --unsorted. All files are headerless.
 --period L or Lx,Ly,Lz (inf: an open axis): the box is periodic, distances are those of the
 minimum image of the coordinate difference (lsknn_tools wrap brings coordinates into one
 period); a radius may not exceed half the period of a finite axis. Not with --point-radii.
+
+--profile R1,R2,...: ascending radii (inf allowed); in place of the lists, the counts at every
+radius from one walk: PREFIX.profile (int32 [nq][B], row-major; column b = the counts of -r
+Rb) and PREFIX.pairs (int64 [B], the column sums: the cumulative pair counts of a two-point
+histogram). --pairs-only writes PREFIX.pairs alone and never holds an [nq][B] array. One line per
+radius is printed: radius, cumulative pairs, pairs in the shell below it.
 
 The index over the points is built once; the queries go through it in chunks of --chunk
 rows. A chunk with more than --max-pairs pairs is split along its counts' prefix sums into
@@ -56,14 +64,29 @@ def add_period_option(ap: argparse.ArgumentParser) -> None:
                     help="periodic box: minimum-image distances (inf: an open axis)")
 
 
+def profile_arg(text: str) -> list[float]:
+    """--profile R1,R2,...: at least one radius, each >= 0, ascending (inf allowed)."""
+    try:
+        vals = [float(v) for v in text.split(",")]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--profile: not a list of numbers: {text!r}") from None
+    if any(math.isnan(v) or v < 0 for v in vals) or any(b < a for a, b in zip(vals, vals[1:])):
+        raise argparse.ArgumentTypeError("--profile: radii must be >= 0, not NaN and ascending")
+    return vals
+
+
 def add_radius_options(ap: argparse.ArgumentParser) -> None:
-    """Exactly one of -r / --radii / --point-radii, --squared and --period (also lsknn_tools rcheck)."""
+    """Exactly one of -r / --radii / --point-radii / --profile, --squared and --period (also
+    lsknn_tools rcheck)."""
     g = ap.add_mutually_exclusive_group(required=True)
     g.add_argument("-r", dest="radius", type=float, default=None, help="one radius for every query")
     g.add_argument("--radii", default=None, metavar="FILE",
                    help="headerless float32 file, one radius per query row: points with dist2 < its square")
     g.add_argument("--point-radii", default=None, metavar="FILE",
                    help="headerless float32 file, one radius per point row: points whose own ball holds the query")
+    g.add_argument("--profile", type=profile_arg, default=None, metavar="R1,R2,...",
+                   help="ascending radii: the counts at every radius (PREFIX.profile) and their sums (PREFIX.pairs)")
+    ap.add_argument("--pairs-only", action="store_true", help="with --profile: PREFIX.pairs only")
     ap.add_argument("--squared", action="store_true", help="the given values are squared cutoffs")
     add_period_option(ap)
 
@@ -97,7 +120,40 @@ def parse(argv: list[str]) -> argparse.Namespace:
         ap.error("--chunk must be at least 1")
     if a.max_pairs < 1:
         ap.error("--max-pairs must be at least 1")
+    if a.pairs_only and a.profile is None:
+        ap.error("--pairs-only needs --profile")
+    if a.profile is not None and (a.counts_only or a.unsorted):
+        ap.error("--profile writes no lists: not with --counts-only / --unsorted")
     return a
+
+
+def run_profile(a: argparse.Namespace, index, nq: int, dev: torch.device, stats) -> list[int] | None:
+    """--profile: PREFIX.profile (unless --pairs-only) and PREFIX.pairs, the queries in chunks;
+    the cumulative pair counts, or None after an error message."""
+    per = {} if a.period is None else {"period": a.period}
+    nb = len(a.profile)
+    gpu = dev.type == "cuda"
+    pairs = [0] * nb  # Python ints: no overflow however many chunks
+    try:
+        E._profile_cutoffs("--profile", a.profile, a.squared, a.period)  # before anything is written
+        if not a.pairs_only:
+            io.write_array(a.out + ".profile", torch.empty(0, dtype=torch.int32), 0, truncate=True, total=nq * nb)
+        for begin in range(0, nq, a.chunk):
+            q = io.read_range(a.queries, begin, min(a.chunk, nq - begin), pin_memory=gpu).to(dev)
+            if a.pairs_only:
+                part = E.pair_counts(index, q, a.profile, squared=a.squared, stats=stats, **per)
+            else:
+                prof = E.radius_profile(index, q, a.profile, squared=a.squared, stats=stats, **per)
+                io.write_array(a.out + ".profile", prof.cpu().reshape(-1), begin * nb, truncate=False)
+                part = prof.sum(0, dtype=torch.int64)
+            pairs = [s + int(v) for s, v in zip(pairs, part.cpu().tolist())]
+    except ValueError as e:
+        sys.stderr.write(f"hipKNN_radius: {e}\n")
+        return None
+    io.write_array(a.out + ".pairs", torch.tensor(pairs, dtype=torch.int64), 0, truncate=True, total=nb)
+    for b, r in enumerate(a.profile):
+        print(f"{r!r} {pairs[b]} {pairs[b] - (pairs[b - 1] if b else 0)}", flush=True)
+    return pairs
 
 
 def split_runs(counts: torch.Tensor, max_pairs: int) -> list[tuple[int, int]]:
@@ -142,6 +198,26 @@ def main(argv: list[str] | None = None) -> int:
     sync()
     t1 = time.perf_counter()
     nq = io.portion(a.queries, 0, 1)[2]
+    if a.profile is not None:
+        sums = run_profile(a, index, nq, dev, stats)
+        if sums is None:
+            return 1
+        sync()
+        t2 = time.perf_counter()
+        if a.verbose:
+            print(f"index of {index.n} points: {t1 - t0:.3f}s; {nq} queries, {len(a.profile)} radii: {t2 - t1:.3f}s  "
+                  f"kernels {E.kernels_used()}", flush=True)
+        if a.stats:
+            rec = {"n": index.n, "nq": nq, "profile": a.profile, "pairs": sums, "chunk": a.chunk,
+                   "device": str(dev), "index_s": t1 - t0, "query_s": t2 - t1, "kernels": E.kernels_used(),
+                   "radius_search": stats.counters}
+            if a.squared:
+                rec["squared"] = True
+            if a.period is not None:
+                rec["period"] = list(a.period)
+            with open(a.stats, "w") as f:
+                json.dump(rec, f, indent=1)
+        return 0
     # the search of queries [b, e) of the file: one radius, one per query (sliced with the
     # queries), or one per point (prepared once)
     try:

@@ -14,6 +14,10 @@
            [--period L | Lx,Ly,Lz]
            -> hipKNN_radius' PREFIX.count (and .offsets / .ids / .dist) for q.float3 against the
               brute-force oracle: every count's consistency with the offsets, sampled rows bitwise
+    python -m mpi_cuda_largescaleknn_amd.apps.tools rcheck in.float3 q.float3 PREFIX --profile R1,R2,... [--squared]
+           [--pairs-only] [--samples S] [--period L | Lx,Ly,Lz]
+           -> hipKNN_radius --profile's PREFIX.profile rows against the brute-force oracle (all rows
+              without --samples when there are at most 65536) and PREFIX.pairs against the column sums
     python -m mpi_cuda_largescaleknn_amd.apps.tools ccheck in.float3 PREFIX -r EPS [--min-pts M] [--squared]
            [--period L | Lx,Ly,Lz]
            -> hipKNN_cluster's PREFIX.labels and PREFIX.core against the brute-force oracle, every
@@ -129,10 +133,65 @@ def _check_neighbors(a, pts, qry, idx) -> int:
     return bad
 
 
+CCHECK_MAX = 65536  # points ccheck (and rows rcheck --profile) takes whole: the oracle visits every pair
+
+
+def _rcheck_profile(a, pts, qry) -> int:
+    """PREFIX.profile / PREFIX.pairs of hipKNN_radius --profile against the oracle."""
+    nq, nb = qry.shape[0], len(a.profile)
+    cut2s = [float(np.float32(r)) if a.squared else cut2_of(r) for r in a.profile]
+    pairs = io.read_array(a.prefix + ".pairs", torch.int64)
+    if pairs.shape[0] != nb:
+        print(f"size mismatch: {pairs.shape[0]} pair counts for {nb} radii")
+        return 1
+    if a.pairs_only:  # no rows to sample: the sums themselves, which visits every pair
+        if nq > CCHECK_MAX:
+            print(f"rcheck: --pairs-only with {nq} queries, more than {CCHECK_MAX}: the oracle visits every pair; "
+                  "check a smaller set, or the profile file")
+            return 1
+        ref = K.pair_counts_cpu(pts, qry, cut2s, a.period)
+        bad = int((pairs != ref).sum())
+        print(f"checked {nb} pair counts: {bad} mismatches")
+        for b in (pairs != ref).nonzero().flatten()[:10].tolist():
+            print(f"PAIRS {b} = {int(pairs[b])} (oracle {int(ref[b])})")
+        return 0 if bad == 0 else 1
+    prof = io.read_array(a.prefix + ".profile", torch.int32)
+    if prof.shape[0] != nq * nb:
+        print(f"size mismatch: {prof.shape[0]} profile entries for {nq} queries x {nb} radii")
+        return 1
+    prof = prof.view(nq, nb)
+    if a.samples is None and nq <= CCHECK_MAX:
+        idx = torch.arange(nq)
+    else:
+        g = torch.Generator().manual_seed(0)
+        samples = 1000 if a.samples is None else a.samples
+        idx = torch.randint(0, nq, (min(samples, nq),), generator=g) if samples < nq else torch.arange(nq)
+    ref = K.radius_profile_cpu(pts, qry[idx], cut2s, a.period)
+    wrong = (prof[idx] != ref).any(dim=1)
+    bad = int(wrong.sum())
+    print(f"checked {idx.numel()} profile rows: {bad} mismatches")
+    for i in wrong.nonzero().flatten()[:10].tolist():
+        b = int((prof[idx[i]] != ref[i]).nonzero()[0])
+        print(f"PROFILE {int(idx[i]):012d} column {b} = {int(prof[idx[i]][b])} (oracle {int(ref[i][b])})")
+    sums = prof.sum(0, dtype=torch.int64)
+    off = (pairs != sums).nonzero().flatten()
+    print(f"checked {nb} pair counts against the column sums: {off.numel()} mismatches")
+    for b in off[:10].tolist():
+        print(f"PAIRS {b} = {int(pairs[b])} (column sum {int(sums[b])})")
+    return 0 if bad + off.numel() == 0 else 1
+
+
 def rcheck(a) -> int:
     pts = io.read_points(a.inp)
     qry = io.read_points(a.queries)
     nq = qry.shape[0]
+    if a.pairs_only and a.profile is None:
+        print("rcheck: --pairs-only needs --profile")
+        return 1
+    if a.profile is not None:
+        return _rcheck_profile(a, pts, qry)
+    if a.samples is None:
+        a.samples = 1000
     if a.period is not None and a.point_radii is not None:
         print("rcheck: --period is not supported with --point-radii")
         return 1
@@ -207,9 +266,6 @@ def rcheck(a) -> int:
                       f"(oracle id {int(wi[j])} dist {wd[j].item()!r})")
     print(f"checked {idx.numel()} sampled rows: {rows_bad} mismatches")
     return 0 if bad + rows_bad == 0 else 1
-
-
-CCHECK_MAX = 65536  # points ccheck takes: its oracle visits every pair
 
 
 def ccheck(a) -> int:
@@ -310,7 +366,8 @@ def main(argv=None) -> int:
     p.add_argument("queries")
     p.add_argument("prefix", help="the -o PREFIX of hipKNN_radius")
     add_radius_options(p)
-    p.add_argument("--samples", type=int, default=1000)
+    p.add_argument("--samples", type=int, default=None,
+                   help="rows compared (default 1000; --profile: every row of up to 65536)")
     p.add_argument("--counts-only", action="store_true")
     p.add_argument("--unsorted", action="store_true", help="rows written with --unsorted: compared as sets")
     p = sub.add_parser("ccheck")

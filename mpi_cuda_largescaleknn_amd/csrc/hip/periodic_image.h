@@ -95,13 +95,22 @@ __device__ __forceinline__ bool far1(float q, float lo, float hi, const Axis &a,
   return wl == s && wh == s;
 }
 
-// All of the node belongs to image I for the lane, and its farthest point is below cut2.
-__device__ __forceinline__ bool box_inside(const lsk::GroupQuery &Q, const float4 &lo4, const float4 &hi4,
-                                           const Axis &X, const Axis &Y, const Axis &Z, const Image &I, float cut2) {
+// All of the node belongs to image I for the lane; far = the canonical dist2 of the per-axis
+// larger |wrapped corner difference|, an upper bound of every point's pd2 when it does.
+__device__ __forceinline__ bool box_far(const lsk::GroupQuery &Q, const float4 &lo4, const float4 &hi4,
+                                        const Axis &X, const Axis &Y, const Axis &Z, const Image &I, float &far) {
   float fx, fy, fz;
   const bool in_x = far1(Q.x, lo4.x, hi4.x, X, I.x.s, fx), in_y = far1(Q.y, lo4.y, hi4.y, Y, I.y.s, fy),
              in_z = far1(Q.z, lo4.z, hi4.z, Z, I.z.s, fz);
-  return in_x && in_y && in_z && lsk::dist2(fx, fy, fz) < cut2;
+  far = lsk::dist2(fx, fy, fz);
+  return in_x && in_y && in_z;
+}
+
+// All of the node belongs to image I for the lane, and its farthest point is below cut2.
+__device__ __forceinline__ bool box_inside(const lsk::GroupQuery &Q, const float4 &lo4, const float4 &hi4,
+                                           const Axis &X, const Axis &Y, const Axis &Z, const Image &I, float cut2) {
+  float far;
+  return box_far(Q, lo4, hi4, X, Y, Z, I, far) && far < cut2;
 }
 
 // The group's three axes against the root box.

@@ -390,6 +390,31 @@ extern "C" void lsk_cpu_radius_periodic_fill(const float *pts, int64_t n, const 
   });
 }
 
+// Radius profile: out[q * nb + b] = #{ i : dist2(q, p_i) < cut2s[b] } for the ascending cutoffs
+// cut2s[0 .. nb), from one pass over the points per query; period (optional): pdist2 instead.
+// A pair goes to shell b0 = #{ b : !(d² < cut2s[b]) } (the cutoffs ascend, so that is the first b
+// with d² < cut2s[b]; a NaN d² passes no test and is dropped), and a row is the running sum of
+// its shells.
+extern "C" void lsk_cpu_radius_profile(const float *pts, int64_t n, const float *qry, int64_t nq,
+                                       const float *cut2s, int32_t nb, const float *period, int32_t *out,
+                                       int nthreads) {
+  const vec3f *P = (const vec3f *)pts;
+  const vec3f *Q = (const vec3f *)qry;
+  if (nb <= 0) return;
+  parallel_for(nq, nthreads, [&](int64_t b, int64_t e) {
+    for (int64_t qi = b; qi < e; qi++) {
+      int32_t *row = out + qi * nb;
+      std::fill(row, row + nb, 0);
+      for (int64_t i = 0; i < n; i++) {
+        const float v = period ? pdist2(Q[qi], P[i], period) : lsk::dist2(Q[qi], P[i]);
+        const float *c = std::partition_point(cut2s, cut2s + nb, [v](float cb) { return !(v < cb); });
+        if (c != cut2s + nb) row[c - cut2s]++;
+      }
+      for (int32_t j = 1; j < nb; j++) row[j] += row[j - 1];
+    }
+  });
+}
+
 // lsk_cpu_kth_brute under a period: the k-th smallest pdist2 among those < cut2, else cut2.
 extern "C" void lsk_cpu_kth_periodic(const float *pts, int64_t n, const float *qry, int64_t nq, int k, float cut2,
                                      const float *period, float *out_d2, int nthreads) {

@@ -117,6 +117,12 @@ void lsk_cpu_radius_periodic_fill(const float *pts, int64_t n, const float *qry,
                                   int32_t *out_idx, float *out_d2, int nthreads);
 void lsk_cpu_cluster_periodic(const float *pts, int64_t n, float cut2, int min_pts, const float *period,
                               int32_t *labels, uint8_t *core, int nthreads);
+// Radius profile by brute force, one pass over the points per query: out[q * nb + b] (int32 [nq,
+// nb]) = #{ i : dist2(q, p_i) < cut2s[b] } for nb >= 1 ascending cutoffs (each >= 0, +inf
+// allowed, no NaN), i.e. column b is lsk_cpu_radius_count at cut2s[b]; period (optional, as
+// above): lsk_cpu_radius_periodic_count at cut2s[b].
+void lsk_cpu_radius_profile(const float *pts, int64_t n, const float *qry, int64_t nq, const float *cut2s,
+                            int32_t nb, const float *period, int32_t *out, int nthreads);
 // lsk_cpu_kth_brute / lsk_cpu_knn_brute under a period: brute force over all points with the
 // periodic squared distance above, the same selection (k-th smallest by bits among those <
 // cut2, else cut2) and the same tie rule (ascending (d² bits, row); unfilled: -1 / cut2).

@@ -1553,6 +1553,141 @@ def radius_self_neighbors(points: torch.Tensor, radius: float | torch.Tensor, so
                                   period=period)
 
 
+# ---- radius profiles: counts at many radii from one walk (radius_profile.hip)
+def _profile_cutoffs(what: str, radii, squared: bool, period) -> tuple:
+    """The checked radii of a profile: (cut2s float32 CPU tensor [B], period values or None).
+    ValueError for no radius, a negative or NaN one, radii that do not ascend, a bad period or
+    a radius above the period's bound; nothing on a device is read."""
+    if isinstance(radii, torch.Tensor):
+        if radii.device.type != "cpu" or radii.dtype not in (torch.float32, torch.float64) or radii.dim() != 1:
+            raise ValueError(f"{what}: radii must be a sequence or a float32 / float64 CPU tensor [B] "
+                             f"(got {radii.dtype} {tuple(radii.shape)} on {radii.device})")
+        vals = radii.tolist()
+    else:
+        try:
+            vals = [float(r) for r in radii]
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: radii must be a sequence of numbers or a CPU tensor") from None
+    if not vals:
+        raise ValueError(f"{what}: radii must hold at least one radius")
+    per = None if period is None else K.check_period(what, period)
+    for r in vals:
+        _radius_cut2(what, r, squared)
+        if per is not None:
+            check_period_radius(what, r, squared, per)
+    if any(b < a for a, b in zip(vals, vals[1:])):
+        raise ValueError(f"{what}: radii must ascend (got {vals})")
+    return torch.tensor([_radius_cut2(what, r, squared) for r in vals], dtype=torch.float32), per
+
+
+def _profile(what: str, index: LocalIndex, queries: torch.Tensor, radii, squared: bool, period,
+             stats: KnnStats | None, sums: bool) -> torch.Tensor:
+    cut2s, per = _profile_cutoffs(what, radii, squared, period)
+    if index.qrot is not None or index.line:
+        raise ValueError(f"{what}: an index built in a rotated frame or sorted by line keys is not supported")
+    queries = _check_foreign(what, index, queries)
+    nq, n, nb = queries.shape[0], index.n, cut2s.shape[0]
+    if nq == 0 or n == 0:
+        if sums:
+            return torch.zeros(nb, dtype=torch.int64, device=index.device)
+        return torch.zeros((nq, nb), dtype=torch.int32, device=index.device)
+    if not K.is_gpu(index.pts):
+        KERNELS_USED.add("cpu")
+        return (K.pair_counts_cpu if sums else K.radius_profile_cpu)(index.pts[:n], queries, cut2s, per)
+    qsorted, qperm = prepare_queries(index, queries, locate=False)[:2]
+    names = _RADIUS_STATS if per is None else _RADIUS_PERIODIC_STATS
+    raw = torch.zeros(len(names), dtype=torch.int64, device=index.device) if stats is not None else None
+    out = (K.pair_counts_gpu if sums else K.radius_profile_gpu)(index.tree(), qsorted, nq, cut2s, qperm, per,
+                                                                stats=raw)
+    KERNELS_USED.add("radius_profile")
+    if stats is not None:
+        for nm, v in zip(names, raw.cpu().tolist()):
+            stats.counters[nm] = stats.counters.get(nm, 0) + int(v)
+    return out
+
+
+def radius_profile(index: LocalIndex, queries: torch.Tensor, radii, squared: bool = False, period=None,
+                   stats: KnnStats | None = None) -> torch.Tensor:
+    """int32 [nq, B], in query order: P[q, b] = the number of points of `index` with dist2(q, p)
+    < cut2_of(radii[b]), strict and cumulative, for B >= 1 ascending radii from one walk of the
+    tree. Column b equals radius_counts(index, queries, radii[b], squared=..., period=...) bit
+    for bit: that is the whole definition; the counts in the shell between two radii are P[:,
+    b] - P[:, b - 1]. radii: a Python sequence or a float32 / float64 CPU tensor, each >= 0,
+    inf and duplicates allowed; squared=True: the squared cutoffs themselves. With `period`
+    dist2 is the minimum image of radius_counts and every radius must respect its bound (half
+    the period of a finite axis). A query with a NaN or infinite coordinate counts nothing in
+    every column. Limit inherited from radius_counts: whole boxes are counted without visiting
+    their points, which is exact for finite indexed points; an *indexed* point with a NaN
+    coordinate is invisible to the tree's boxes, so a box that is accepted whole counts it
+    (and the two functions need not accept the same boxes: the column identity holds for
+    finite indexed points).
+
+    No radius, a negative or NaN radius, radii that do not ascend, a radius above the period's
+    bound and the failures of radius_counts' own argument checks raise ValueError before any
+    kernel runs, without a device read. An index built in a rotated frame or sorted by line
+    keys is not supported. `stats` receives radius_evals / radius_nodes / radius_buckets /
+    radius_box_accepts, and radius_images under a period. More than 32 radii are served in
+    slices of 32, one walk each."""
+    return _profile("radius_profile", index, queries, radii, squared, period, stats, False)
+
+
+def pair_counts(index: LocalIndex, queries: torch.Tensor, radii, squared: bool = False, period=None,
+                stats: KnnStats | None = None) -> torch.Tensor:
+    """int64 [B] on the index's device: S[b] = the sum over all queries of radius_profile's P[q,
+    b], the cumulative pair counts DR(< r_b) of a two-point histogram (shell b holds S[b] - S[b
+    - 1] pairs), without ever allocating anything of size nq x B. Integer sums: two runs give
+    the same bits. Arguments and errors as for radius_profile."""
+    return _profile("pair_counts", index, queries, radii, squared, period, stats, True)
+
+
+def _profile_index(what: str, points: torch.Tensor, queries: torch.Tensor, radii, squared: bool,
+                   period) -> LocalIndex | None:
+    """The index of the *_query_* / *_self_* profile forms; None when there is nothing to index
+    (the radii are checked all the same)."""
+    if points.device != queries.device:
+        raise ValueError(f"{what}: points on {points.device}, queries on {queries.device}")
+    if points.shape[0] == 0:
+        _profile_cutoffs(what, radii, squared, period)
+        return None
+    return build_index(points)
+
+
+def radius_query_profile(points: torch.Tensor, queries: torch.Tensor, radii, squared: bool = False, period=None,
+                         stats: KnnStats | None = None) -> torch.Tensor:
+    """radius_profile over an index built once from `points` (both float32 [*, 3] on one
+    device), in the points' own frame."""
+    index = _profile_index("radius_query_profile", points, queries, radii, squared, period)
+    if index is None:
+        return torch.zeros((queries.shape[0], len(radii)), dtype=torch.int32, device=queries.device)
+    return radius_profile(index, queries, radii, squared=squared, period=period, stats=stats)
+
+
+def radius_self_profile(points: torch.Tensor, radii, squared: bool = False, period=None,
+                        stats: KnnStats | None = None) -> torch.Tensor:
+    """radius_query_profile with the points as their own queries: every finite point counts
+    itself (and its exact copies) at every radius > 0."""
+    return radius_query_profile(points, points, radii, squared=squared, period=period, stats=stats)
+
+
+def pair_query_counts(points: torch.Tensor, queries: torch.Tensor, radii, squared: bool = False, period=None,
+                      stats: KnnStats | None = None) -> torch.Tensor:
+    """pair_counts over an index built once from `points`, in the points' own frame."""
+    index = _profile_index("pair_query_counts", points, queries, radii, squared, period)
+    if index is None:
+        return torch.zeros(len(radii), dtype=torch.int64, device=queries.device)
+    return pair_counts(index, queries, radii, squared=squared, period=period, stats=stats)
+
+
+def pair_self_counts(points: torch.Tensor, radii, squared: bool = False, period=None,
+                     stats: KnnStats | None = None) -> torch.Tensor:
+    """pair_query_counts with the points as their own queries. S[b] counts ordered pairs, (p, q)
+    and (q, p) both, and every finite point with itself (at every radius > 0). The unordered
+    pair count of a DD histogram is the caller's step, not the library's: DD_unordered = (S -
+    S_at_zero_distance) / 2, where S_at_zero_distance is the count at the smallest radius above
+    0 that separates nothing but exact copies (n for a set without duplicates)."""
+    return pair_query_counts(points, points, radii, squared=squared, period=period, stats=stats)
+
+
 def _no_period(what: str, period) -> None:
     if period is not None:
         raise ValueError(f"{what}: a period is not supported for per-point radii")

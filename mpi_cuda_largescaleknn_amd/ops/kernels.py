@@ -1067,6 +1067,97 @@ def cluster_periodic_gpu(tree: tuple, perm: torch.Tensor, core_sorted: torch.Ten
     return labels, err
 
 
+# --------------------------------------------------------------------------- radius profiles
+PROFILE_BINS = 32  # radius_profile.hip kProfileBins: cutoffs per launch, longer lists go in slices
+
+
+def _profile_cut2s(what: str, cut2s) -> torch.Tensor:
+    """The ascending squared cutoffs of a profile as a float32 CPU tensor [B], B >= 1."""
+    c = torch.as_tensor(cut2s, dtype=torch.float32, device="cpu").contiguous()
+    if c.dim() != 1 or c.shape[0] < 1:
+        raise ValueError(f"{what}: cut2s must hold at least one cutoff (got shape {tuple(c.shape)})")
+    if not bool((c >= 0).all()) or not bool((c[1:] >= c[:-1]).all()):  # (a NaN fails both)
+        raise ValueError(f"{what}: cut2s must be >= 0, not NaN and ascending")
+    return c
+
+
+def radius_profile_cpu(points: torch.Tensor, queries: torch.Tensor, cut2s, period=None) -> torch.Tensor:
+    """CPU oracle (brute force, one pass over the points per query): int32 [nq, B], column b =
+    the number of rows of `points` with dist2 < cut2s[b] (strict), i.e. radius_count_cpu at that
+    cutoff; with `period`, radius_periodic_count_cpu at that cutoff. cut2s: B >= 1 ascending
+    squared cutoffs (a sequence or a CPU tensor)."""
+    c = _profile_cut2s("radius_profile_cpu", cut2s)
+    per = None if period is None else check_period("radius_profile_cpu", period)
+    pts = points.contiguous().float().cpu()
+    q = queries.contiguous().float().cpu()
+    out = torch.empty((q.shape[0], c.shape[0]), dtype=torch.int32)
+    _native.host().lsk_cpu_radius_profile(_ptr(pts), pts.shape[0], _ptr(q), q.shape[0], _ptr(c), c.shape[0],
+                                          None if per is None else _period_c(per), _ptr(out), _nthreads())
+    return out
+
+
+def pair_counts_cpu(points: torch.Tensor, queries: torch.Tensor, cut2s, period=None) -> torch.Tensor:
+    """CPU oracle of the pair counts: int64 [B], the column sums of radius_profile_cpu."""
+    return radius_profile_cpu(points, queries, cut2s, period).sum(0, dtype=torch.int64)
+
+
+def _profile_stats(what: str, stats: torch.Tensor | None, period, dev: torch.device) -> None:
+    need = RADIUS_PERIODIC_STATS if period is not None else 4
+    if stats is not None and (stats.dtype != torch.int64 or stats.numel() < need or stats.device != dev):
+        raise ValueError(f"{what}: stats int64 [{need}] on the tree's device")
+
+
+def radius_profile_gpu(tree: tuple, qsorted: torch.Tensor, nq: int, cut2s, out_perm: torch.Tensor,
+                       period: tuple[float, float, float] | None = None,
+                       stats: torch.Tensor | None = None) -> torch.Tensor:
+    """The radius profile (radius_profile.hip) on the current stream: int32 [nq, B] in query
+    order, column b = radius_count_gpu (period: radius_periodic_count_gpu) at cut2s[b], from one
+    walk per slice of up to PROFILE_BINS cutoffs; every slice writes its own columns of the
+    result. tree / qsorted / out_perm as for radius_count_gpu; cut2s: B >= 1 ascending squared
+    cutoffs on the host (within the period's bound: the caller checks). stats: optional zeroed
+    int64 [4] (period: [RADIUS_PERIODIC_STATS]), summed over the slices."""
+    c = _profile_cut2s("radius_profile_gpu", cut2s)
+    tv = _walk_view("radius_profile_gpu", tree, qsorted, nq, out_perm)
+    dev = tree[0].device
+    _profile_stats("radius_profile_gpu", stats, period, dev)
+    nb = c.shape[0]
+    out = torch.empty((nq, nb), dtype=torch.int32, device=dev)
+    cdev = c.to(dev)
+    per = None if period is None else _period_c(period)
+    lib = _native.hip()
+    for col0 in range(0, nb, PROFILE_BINS):
+        m = min(PROFILE_BINS, nb - col0)
+        check(lib.lsk_hip_radius_profile(C.byref(tv), _ptr(qsorted), int(nq), cdev.data_ptr() + 4 * col0, m, per,
+                                         _ptr(out_perm), _ptr(out), nb, col0, _ptr(stats), _stream(tree[0])),
+              "radius_profile")
+    return out
+
+
+def pair_counts_gpu(tree: tuple, qsorted: torch.Tensor, nq: int, cut2s, out_perm: torch.Tensor,
+                    period: tuple[float, float, float] | None = None,
+                    stats: torch.Tensor | None = None) -> torch.Tensor:
+    """The pair counts (radius_profile.hip, sum mode) on the current stream: int64 [B] on the
+    tree's device, the column sums of radius_profile_gpu, without its [nq, B] array: every block
+    writes one row of bin sums into a workspace of nq / 256 rows, which one small kernel adds.
+    Arguments as for radius_profile_gpu."""
+    c = _profile_cut2s("pair_counts_gpu", cut2s)
+    tv = _walk_view("pair_counts_gpu", tree, qsorted, nq, out_perm)
+    dev = tree[0].device
+    _profile_stats("pair_counts_gpu", stats, period, dev)
+    nb = c.shape[0]
+    sums = torch.zeros(nb, dtype=torch.int64, device=dev)
+    cdev = c.to(dev)
+    per = None if period is None else _period_c(period)
+    lib = _native.hip()
+    ws = torch.empty(int(lib.lsk_hip_pair_counts_ws_bytes(int(nq))) // 8, dtype=torch.int64, device=dev)
+    for col0 in range(0, nb, PROFILE_BINS):
+        m = min(PROFILE_BINS, nb - col0)
+        check(lib.lsk_hip_pair_counts(C.byref(tv), _ptr(qsorted), int(nq), cdev.data_ptr() + 4 * col0, m, per,
+                                      _ptr(out_perm), _ptr(ws), _ptr(sums), col0, _ptr(stats), _stream(tree[0])),
+              "pair_counts")
+    return sums
+
+
 # --------------------------------------------------------------------------- periodic k-NN
 def kth_periodic_cpu(points: torch.Tensor, queries: torch.Tensor, k: int, cut2: float, period) -> torch.Tensor:
     """CPU oracle (brute force): kth_cpu with the periodic squared distance of
