@@ -4,6 +4,7 @@
                   -o <PREFIX> [--counts-only] [--unsorted] [--chunk N] [--max-pairs M]
                   [--period L | Lx,Ly,Lz] [--device auto|cuda|cpu] [--stats f.json] [-v]
     hipKNN_radius <points.float3> <queries.float3> --profile R1,R2,... [--squared] -o <PREFIX> [--pairs-only]
+                  [--weights W.i64 [--query-weights WQ.i64]]
                   [--chunk N] [--period L | Lx,Ly,Lz] [--device auto|cuda|cpu] [--stats f.json] [-v]
 
 For every row of the query file, the points of the point file with dist2 < radius² (float32
@@ -25,6 +26,14 @@ radius from one walk: PREFIX.profile (int32 [nq][B], row-major; column b = the c
 Rb) and PREFIX.pairs (int64 [B], the column sums: the cumulative pair counts of a two-point
 histogram). --pairs-only writes PREFIX.pairs alone and never holds an [nq][B] array. One line per
 radius is printed: radius, cumulative pairs, pairs in the shell below it.
+
+--profile with --weights W.i64 (a headerless little-endian int64 file, one weight per point row,
+negative allowed): in place of the counts, the exact sums of the weights within every radius,
+PREFIX.wprofile (int64 [nq][B]) and PREFIX.wpairs (int64 [B], the sums over the queries, each row
+times its weight of --query-weights WQ.i64, one int64 per query row; without it 1). The weights are
+prepared once for all chunks; max|w| * n must be below 2^62 and (sum |w|) * (sum |wq|) below 2^63
+(lsknn_tools fixweights turns float masses into such weights). One line per radius: radius,
+cumulative sum, sum of the shell below it. Without --weights nothing about --profile changes.
 
 The index over the points is built once; the queries go through it in chunks of --chunk
 rows. A chunk with more than --max-pairs pairs is split along its counts' prefix sums into
@@ -86,7 +95,12 @@ def add_radius_options(ap: argparse.ArgumentParser) -> None:
                    help="headerless float32 file, one radius per point row: points whose own ball holds the query")
     g.add_argument("--profile", type=profile_arg, default=None, metavar="R1,R2,...",
                    help="ascending radii: the counts at every radius (PREFIX.profile) and their sums (PREFIX.pairs)")
-    ap.add_argument("--pairs-only", action="store_true", help="with --profile: PREFIX.pairs only")
+    ap.add_argument("--pairs-only", action="store_true", help="with --profile: PREFIX.pairs (.wpairs) only")
+    ap.add_argument("--weights", default=None, metavar="W.i64",
+                    help="with --profile: headerless int64 file, one weight per point row: the sums of the weights "
+                         "within every radius (PREFIX.wprofile, PREFIX.wpairs)")
+    ap.add_argument("--query-weights", default=None, metavar="WQ.i64",
+                    help="with --weights: headerless int64 file, one weight per query row, for PREFIX.wpairs")
     ap.add_argument("--squared", action="store_true", help="the given values are squared cutoffs")
     add_period_option(ap)
 
@@ -97,6 +111,21 @@ def read_radii(path: str, what: str, rows: int, of: str) -> torch.Tensor:
     if r.shape[0] != rows:
         raise ValueError(f"{what} {path} holds {r.shape[0]} values, {of} has {rows} rows")
     return r
+
+
+def read_weights(path: str, what: str, rows: int, of: str) -> torch.Tensor:
+    """A weight file of `rows` int64 values; ValueError names both lengths otherwise."""
+    w = io.read_array(path, torch.int64)
+    if w.shape[0] != rows:
+        raise ValueError(f"{what} {path} holds {w.shape[0]} values, {of} has {rows} rows")
+    return w
+
+
+def check_weight_options(ap: argparse.ArgumentParser, a: argparse.Namespace) -> None:
+    if a.weights is not None and a.profile is None:
+        ap.error("--weights needs --profile")
+    if a.query_weights is not None and a.weights is None:
+        ap.error("--query-weights needs --weights")
 
 
 def parse(argv: list[str]) -> argparse.Namespace:
@@ -122,6 +151,7 @@ def parse(argv: list[str]) -> argparse.Namespace:
         ap.error("--max-pairs must be at least 1")
     if a.pairs_only and a.profile is None:
         ap.error("--pairs-only needs --profile")
+    check_weight_options(ap, a)
     if a.profile is not None and (a.counts_only or a.unsorted):
         ap.error("--profile writes no lists: not with --counts-only / --unsorted")
     return a
@@ -154,6 +184,41 @@ def run_profile(a: argparse.Namespace, index, nq: int, dev: torch.device, stats)
     for b, r in enumerate(a.profile):
         print(f"{r!r} {pairs[b]} {pairs[b] - (pairs[b - 1] if b else 0)}", flush=True)
     return pairs
+
+
+def run_weighted_profile(a: argparse.Namespace, index, nq: int, dev: torch.device, stats) -> list[int] | None:
+    """--profile --weights: PREFIX.wprofile (unless --pairs-only) and PREFIX.wpairs, the weights
+    prepared once and the queries in chunks; the cumulative weighted pair sums, or None after an
+    error message."""
+    per = {} if a.period is None else {"period": a.period}
+    nb = len(a.profile)
+    gpu = dev.type == "cuda"
+    sums = [0] * nb
+    try:
+        E._profile_cutoffs("--profile", a.profile, a.squared, a.period)  # before anything is written
+        pw = E.prepare_point_weights(index, read_weights(a.weights, "--weights", index.n, a.points).to(dev))
+        wq = None if a.query_weights is None else read_weights(a.query_weights, "--query-weights", nq, a.queries)
+        E.check_pair_sum_bound("--weights", pw, wq, nq)  # the whole file's bound: PREFIX.wpairs holds int64
+        if not a.pairs_only:
+            io.write_array(a.out + ".wprofile", torch.empty(0, dtype=torch.int64), 0, truncate=True, total=nq * nb)
+        for begin in range(0, nq, a.chunk):
+            q = io.read_range(a.queries, begin, min(a.chunk, nq - begin), pin_memory=gpu).to(dev)
+            wqc = None if wq is None else wq[begin:begin + q.shape[0]].to(dev)
+            if a.pairs_only:
+                part = E.weighted_pair_sums(index, q, a.profile, pw, query_weights=wqc, squared=a.squared,
+                                            stats=stats, **per)
+            else:
+                prof = E.weighted_profile(index, q, a.profile, pw, squared=a.squared, stats=stats, **per)
+                io.write_array(a.out + ".wprofile", prof.cpu().reshape(-1), begin * nb, truncate=False)
+                part = (prof if wqc is None else prof * wqc[:, None]).sum(0, dtype=torch.int64)
+            sums = [s + int(v) for s, v in zip(sums, part.cpu().tolist())]
+    except ValueError as e:
+        sys.stderr.write(f"hipKNN_radius: {e}\n")
+        return None
+    io.write_array(a.out + ".wpairs", torch.tensor(sums, dtype=torch.int64), 0, truncate=True, total=nb)
+    for b, r in enumerate(a.profile):
+        print(f"{r!r} {sums[b]} {sums[b] - (sums[b - 1] if b else 0)}", flush=True)
+    return sums
 
 
 def split_runs(counts: torch.Tensor, max_pairs: int) -> list[tuple[int, int]]:
@@ -199,7 +264,7 @@ def main(argv: list[str] | None = None) -> int:
     t1 = time.perf_counter()
     nq = io.portion(a.queries, 0, 1)[2]
     if a.profile is not None:
-        sums = run_profile(a, index, nq, dev, stats)
+        sums = (run_profile if a.weights is None else run_weighted_profile)(a, index, nq, dev, stats)
         if sums is None:
             return 1
         sync()
@@ -211,6 +276,8 @@ def main(argv: list[str] | None = None) -> int:
             rec = {"n": index.n, "nq": nq, "profile": a.profile, "pairs": sums, "chunk": a.chunk,
                    "device": str(dev), "index_s": t1 - t0, "query_s": t2 - t1, "kernels": E.kernels_used(),
                    "radius_search": stats.counters}
+            if a.weights is not None:
+                rec.update({"weights": a.weights, "query_weights": a.query_weights})
             if a.squared:
                 rec["squared"] = True
             if a.period is not None:

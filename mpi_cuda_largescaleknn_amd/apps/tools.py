@@ -18,6 +18,13 @@
            [--pairs-only] [--samples S] [--period L | Lx,Ly,Lz]
            -> hipKNN_radius --profile's PREFIX.profile rows against the brute-force oracle (all rows
               without --samples when there are at most 65536) and PREFIX.pairs against the column sums
+    python -m mpi_cuda_largescaleknn_amd.apps.tools rcheck in.float3 q.float3 PREFIX --profile R1,R2,... --weights W.i64
+           [--query-weights WQ.i64] [--pairs-only] ...
+           -> hipKNN_radius --profile --weights' PREFIX.wprofile and PREFIX.wpairs against the oracle, on
+              the same sampling rules
+    python -m mpi_cuda_largescaleknn_amd.apps.tools fixweights in.float out.i64 [--bits N] [--terms T]
+           -> float32 masses as exact fixed-point int64 weights
+              (knn_engine.fixed_point_weights); prints the exponent s: physical sum = result * 2^s
     python -m mpi_cuda_largescaleknn_amd.apps.tools ccheck in.float3 PREFIX -r EPS [--min-pts M] [--squared]
            [--period L | Lx,Ly,Lz]
            -> hipKNN_cluster's PREFIX.labels and PREFIX.core against the brute-force oracle, every
@@ -36,7 +43,7 @@ import sys
 import numpy as np
 import torch
 
-from ..models.knn_engine import cut2_of, wrap_points
+from ..models.knn_engine import cut2_of, fixed_point_weights, wrap_points
 from ..ops import kernels as K
 from ..utils import io
 
@@ -181,6 +188,71 @@ def _rcheck_profile(a, pts, qry) -> int:
     return 0 if bad + off.numel() == 0 else 1
 
 
+def _rcheck_weighted(a, pts, qry) -> int:
+    """PREFIX.wprofile / PREFIX.wpairs of hipKNN_radius --profile --weights against the oracle,
+    on the sampling rules of _rcheck_profile."""
+    from .radius import read_weights
+    nq, nb = qry.shape[0], len(a.profile)
+    cut2s = [float(np.float32(r)) if a.squared else cut2_of(r) for r in a.profile]
+    try:
+        w = read_weights(a.weights, "--weights", pts.shape[0], a.inp)
+        wq = None if a.query_weights is None else read_weights(a.query_weights, "--query-weights", nq, a.queries)
+    except ValueError as e:
+        print(f"rcheck: {e}")
+        return 1
+    pairs = io.read_array(a.prefix + ".wpairs", torch.int64)
+    if pairs.shape[0] != nb:
+        print(f"size mismatch: {pairs.shape[0]} pair sums for {nb} radii")
+        return 1
+    if a.pairs_only:  # no rows to sample: the sums themselves, which visits every pair
+        if nq > CCHECK_MAX:
+            print(f"rcheck: --pairs-only with {nq} queries, more than {CCHECK_MAX}: the oracle visits every pair; "
+                  "check a smaller set, or the profile file")
+            return 1
+        ref = K.weighted_pair_sums_cpu(pts, qry, cut2s, w, a.period, query_weights=wq)
+        bad = int((pairs != ref).sum())
+        print(f"checked {nb} weighted pair sums: {bad} mismatches")
+        for b in (pairs != ref).nonzero().flatten()[:10].tolist():
+            print(f"WPAIRS {b} = {int(pairs[b])} (oracle {int(ref[b])})")
+        return 0 if bad == 0 else 1
+    prof = io.read_array(a.prefix + ".wprofile", torch.int64)
+    if prof.shape[0] != nq * nb:
+        print(f"size mismatch: {prof.shape[0]} profile entries for {nq} queries x {nb} radii")
+        return 1
+    prof = prof.view(nq, nb)
+    if a.samples is None and nq <= CCHECK_MAX:
+        idx = torch.arange(nq)
+    else:
+        g = torch.Generator().manual_seed(0)
+        samples = 1000 if a.samples is None else a.samples
+        idx = torch.randint(0, nq, (min(samples, nq),), generator=g) if samples < nq else torch.arange(nq)
+    ref = K.weighted_profile_cpu(pts, qry[idx], cut2s, w, a.period)
+    wrong = (prof[idx] != ref).any(dim=1)
+    bad = int(wrong.sum())
+    print(f"checked {idx.numel()} weighted profile rows: {bad} mismatches")
+    for i in wrong.nonzero().flatten()[:10].tolist():
+        b = int((prof[idx[i]] != ref[i]).nonzero()[0])
+        print(f"WPROFILE {int(idx[i]):012d} column {b} = {int(prof[idx[i]][b])} (oracle {int(ref[i][b])})")
+    sums = (prof if wq is None else prof * wq[:, None]).sum(0, dtype=torch.int64)
+    off = (pairs != sums).nonzero().flatten()
+    print(f"checked {nb} weighted pair sums against the weighted column sums: {off.numel()} mismatches")
+    for b in off[:10].tolist():
+        print(f"WPAIRS {b} = {int(pairs[b])} (column sum {int(sums[b])})")
+    return 0 if bad + off.numel() == 0 else 1
+
+
+def fixweights(a) -> int:
+    w = io.read_array(a.inp, torch.float32)
+    try:
+        fix, s = fixed_point_weights(w, n_terms=a.terms, bits=a.bits)
+    except ValueError as e:
+        print(f"fixweights: {e}")
+        return 1
+    io.write_array(a.out, fix, 0, truncate=True, total=fix.shape[0])
+    print(f"wrote {fix.shape[0]} int64 weights to {a.out}: s = {s} (physical value = weight * 2^{s})")
+    return 0
+
+
 def rcheck(a) -> int:
     pts = io.read_points(a.inp)
     qry = io.read_points(a.queries)
@@ -188,6 +260,11 @@ def rcheck(a) -> int:
     if a.pairs_only and a.profile is None:
         print("rcheck: --pairs-only needs --profile")
         return 1
+    if (a.weights is not None and a.profile is None) or (a.query_weights is not None and a.weights is None):
+        print("rcheck: --weights needs --profile, --query-weights needs --weights")
+        return 1
+    if a.profile is not None and a.weights is not None:
+        return _rcheck_weighted(a, pts, qry)
     if a.profile is not None:
         return _rcheck_profile(a, pts, qry)
     if a.samples is None:
@@ -370,6 +447,11 @@ def main(argv=None) -> int:
                    help="rows compared (default 1000; --profile: every row of up to 65536)")
     p.add_argument("--counts-only", action="store_true")
     p.add_argument("--unsorted", action="store_true", help="rows written with --unsorted: compared as sets")
+    p = sub.add_parser("fixweights")
+    p.add_argument("inp", help="headerless float32 file of weights (masses)")
+    p.add_argument("out", help="headerless int64 file")
+    p.add_argument("--bits", type=int, default=62, help="sum |w_fix| <= 2^bits (default 62; pair sums: split them)")
+    p.add_argument("--terms", type=int, default=None, help="weights that can meet in one sum (default: the file's)")
     p = sub.add_parser("ccheck")
     p.add_argument("inp")
     p.add_argument("prefix", help="the -o PREFIX of hipKNN_cluster")
@@ -394,7 +476,7 @@ def main(argv=None) -> int:
     if a.cmd == "wrap" and a.period is None:
         ap.error("wrap: --period is required")
     return {"gen": gen, "split": split, "check": check, "rcheck": rcheck, "ccheck": ccheck, "wrap": wrap, "cat": cat,
-            "cmp": cmp}[a.cmd](a)
+            "cmp": cmp, "fixweights": fixweights}[a.cmd](a)
 
 
 if __name__ == "__main__":

@@ -415,6 +415,33 @@ extern "C" void lsk_cpu_radius_profile(const float *pts, int64_t n, const float 
   });
 }
 
+// Weighted radius profile: out[q * nb + b] = the sum of w[i] over { i : dist2(q, p_i) < cut2s[b] },
+// the walk of lsk_cpu_radius_profile with the point's int64 weight added to its shell in the
+// place of 1. Wrapping 64-bit sums: exact whenever the true sums fit (the caller's check).
+extern "C" void lsk_cpu_weighted_profile(const float *pts, int64_t n, const float *qry, int64_t nq,
+                                         const float *cut2s, int32_t nb, const float *period, const int64_t *w,
+                                         int64_t *out, int nthreads) {
+  const vec3f *P = (const vec3f *)pts;
+  const vec3f *Q = (const vec3f *)qry;
+  if (nb <= 0) return;
+  parallel_for(nq, nthreads, [&](int64_t b, int64_t e) {
+    std::vector<uint64_t> shell((size_t)nb);
+    for (int64_t qi = b; qi < e; qi++) {
+      std::fill(shell.begin(), shell.end(), (uint64_t)0);
+      for (int64_t i = 0; i < n; i++) {
+        const float v = period ? pdist2(Q[qi], P[i], period) : lsk::dist2(Q[qi], P[i]);
+        const float *c = std::partition_point(cut2s, cut2s + nb, [v](float cb) { return !(v < cb); });
+        if (c != cut2s + nb) shell[c - cut2s] += (uint64_t)w[i];
+      }
+      uint64_t run = 0;
+      for (int32_t j = 0; j < nb; j++) {
+        run += shell[j];
+        out[qi * nb + j] = (int64_t)run;
+      }
+    }
+  });
+}
+
 // lsk_cpu_kth_brute under a period: the k-th smallest pdist2 among those < cut2, else cut2.
 extern "C" void lsk_cpu_kth_periodic(const float *pts, int64_t n, const float *qry, int64_t nq, int k, float cut2,
                                      const float *period, float *out_d2, int nthreads) {

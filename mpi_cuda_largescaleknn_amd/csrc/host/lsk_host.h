@@ -123,6 +123,11 @@ void lsk_cpu_cluster_periodic(const float *pts, int64_t n, float cut2, int min_p
 // above): lsk_cpu_radius_periodic_count at cut2s[b].
 void lsk_cpu_radius_profile(const float *pts, int64_t n, const float *qry, int64_t nq, const float *cut2s,
                             int32_t nb, const float *period, int32_t *out, int nthreads);
+// The same with a weight per point: out[q * nb + b] (int64 [nq, nb]) = the sum of w[i] (int64 [n],
+// negative allowed) over { i : dist2(q, p_i) < cut2s[b] }; with every weight 1 the counts above.
+// Sums wrap in 64 bits: exact when sum |w| < 2^63.
+void lsk_cpu_weighted_profile(const float *pts, int64_t n, const float *qry, int64_t nq, const float *cut2s,
+                              int32_t nb, const float *period, const int64_t *w, int64_t *out, int nthreads);
 // lsk_cpu_kth_brute / lsk_cpu_knn_brute under a period: brute force over all points with the
 // periodic squared distance above, the same selection (k-th smallest by bits among those <
 // cut2, else cut2) and the same tie rule (ascending (d² bits, row); unfilled: -1 / cut2).

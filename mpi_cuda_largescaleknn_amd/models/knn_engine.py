@@ -1688,6 +1688,254 @@ def pair_self_counts(points: torch.Tensor, radii, squared: bool = False, period=
     return pair_query_counts(points, points, radii, squared=squared, period=period, stats=stats)
 
 
+# ---- weighted radius profiles: exact sums of int64 point weights within radii (weighted_profile.hip)
+def _max_abs(w: torch.Tensor) -> int:
+    """max |w| of an int64 tensor as a Python int (one small reduction is read; |-2^63| included)."""
+    if w.numel() == 0:
+        return 0
+    lo, hi = torch.stack(torch.aminmax(w)).tolist()
+    return max(-lo, hi)
+
+
+def _abs_sum(w: torch.Tensor) -> int:
+    """sum |w| of an int64 tensor (fewer than 2^31 entries) as an exact Python int, whatever its
+    entries: the high and the low 32 bits of the positive and of the negative entries are summed
+    apart (each sum fits int64) and put together on the host. One small read."""
+    if w.numel() == 0:
+        return 0
+    zero = torch.zeros((), dtype=torch.int64, device=w.device)
+    parts = []
+    for part in (torch.where(w > 0, w, zero), torch.where(w < 0, w, zero)):
+        parts += [(part >> 32).sum(), (part & 0xFFFFFFFF).sum()]
+    ph, pl, nh, nl = torch.stack(parts).tolist()
+    return ((ph << 32) + pl) - ((nh << 32) + nl)
+
+
+@dataclass
+class PointWeights:
+    """Per-point int64 weights prepared for one index (prepare_point_weights)."""
+    index: LocalIndex
+    weights: torch.Tensor                # int64 [n], rows of the indexed array
+    sorted: torch.Tensor                 # the same in the index's curve order (weights[index.perm[:n]])
+    prefix: torch.Tensor | None          # GPU index: int64 [n + 1] exclusive prefix sum of `sorted`
+    abs_sum: int                         # A_p = sum |w|, exact
+
+
+def prepare_point_weights(index: LocalIndex, weights: torch.Tensor) -> PointWeights:
+    """Per-point weights (int64 [n] on the index's device, in the order of the indexed array's
+    rows, negative allowed) made ready for the weighted_* functions over `index`: the weights in
+    curve order and, on a GPU index, their exclusive prefix sum W (int64 [n + 1], W[0] = 0), from
+    which a tree node that is accepted whole takes its weight. max|w| * n must be below 2^62
+    (ValueError otherwise; one small device reduction is read): every sum of weights is then
+    exact in int64. The index itself is not written. Every weighted_* function that takes an
+    index accepts the result in place of the tensor, so a caller that sends queries in chunks
+    prepares the weights once."""
+    what = "prepare_point_weights"
+    n = index.n
+    w = K.int64_weights(what, "weights", weights, n, index.device)
+    top = _max_abs(w)
+    if top * n >= 1 << 62:
+        raise ValueError(f"{what}: max|w| * n must be below 2^62 for exact int64 sums (max|w| = {top}, n = {n})")
+    abs_sum = int(w.abs().sum()) if n else 0  # (cannot wrap: at most max|w| * n)
+    wsorted = w[index.perm[:n].long()].contiguous()
+    prefix = None
+    if K.is_gpu(index.pts):
+        prefix = torch.zeros(n + 1, dtype=torch.int64, device=index.device)
+        torch.cumsum(wsorted, 0, out=prefix[1:])
+    return PointWeights(index, w, wsorted, prefix, abs_sum)
+
+
+def check_pair_sum_bound(what: str, weights: PointWeights, query_weights: torch.Tensor | None, nq: int) -> None:
+    """The bound of the weighted pair sums: (sum |weights|) * (sum |query_weights|) < 2^63, with nq
+    in the place of the second sum when there are no query weights (int64 [nq], on any device;
+    one small read); ValueError otherwise. Every partial sum of wq * w over pairs is then exact in
+    int64. The CLI applies it to a whole query file before it sends the chunks."""
+    a_q = nq if query_weights is None else _abs_sum(query_weights)
+    if weights.abs_sum * a_q >= 1 << 63:
+        raise ValueError(f"{what}: (sum |weights|) * (sum |query_weights|) must be below 2^63 for exact int64 "
+                         f"pair sums (got {weights.abs_sum} * {a_q})")
+
+
+def _point_weights(what: str, index: LocalIndex, weights) -> PointWeights:
+    if isinstance(weights, PointWeights):
+        if weights.index is not index:
+            raise ValueError(f"{what}: the point weights were prepared for another index")
+        return weights
+    try:
+        return prepare_point_weights(index, weights)
+    except ValueError as e:
+        raise ValueError(str(e).replace("prepare_point_weights", what, 1)) from None
+
+
+def _weighted(what: str, index: LocalIndex, queries: torch.Tensor, radii, weights, query_weights, squared: bool,
+              period, stats: KnnStats | None, sums: bool) -> torch.Tensor:
+    cut2s, per = _profile_cutoffs(what, radii, squared, period)
+    if index.qrot is not None or index.line:
+        raise ValueError(f"{what}: an index built in a rotated frame or sorted by line keys is not supported")
+    queries = _check_foreign(what, index, queries)
+    nq, n, nb = queries.shape[0], index.n, cut2s.shape[0]
+    pw = _point_weights(what, index, weights)
+    wq = None
+    if sums:
+        if query_weights is not None:
+            wq = K.int64_weights(what, "query_weights", query_weights, nq, index.device)
+        check_pair_sum_bound(what, pw, wq, nq)
+    if nq == 0 or n == 0:
+        if sums:
+            return torch.zeros(nb, dtype=torch.int64, device=index.device)
+        return torch.zeros((nq, nb), dtype=torch.int64, device=index.device)
+    if not K.is_gpu(index.pts):
+        KERNELS_USED.add("cpu")
+        if sums:
+            return K.weighted_pair_sums_cpu(index.pts[:n], queries, cut2s, pw.sorted, per, query_weights=wq)
+        return K.weighted_profile_cpu(index.pts[:n], queries, cut2s, pw.sorted, per)
+    qsorted, qperm = prepare_queries(index, queries, locate=False)[:2]
+    names = _RADIUS_STATS if per is None else _RADIUS_PERIODIC_STATS
+    raw = torch.zeros(len(names), dtype=torch.int64, device=index.device) if stats is not None else None
+    if sums:
+        out = K.weighted_pair_sums_gpu(index.tree(), qsorted, nq, cut2s, qperm, pw.sorted, pw.prefix,
+                                       query_weights=wq, period=per, stats=raw)
+    else:
+        out = K.weighted_profile_gpu(index.tree(), qsorted, nq, cut2s, qperm, pw.sorted, pw.prefix, period=per,
+                                     stats=raw)
+    KERNELS_USED.add("weighted_profile")
+    if stats is not None:
+        for nm, v in zip(names, raw.cpu().tolist()):
+            stats.counters[nm] = stats.counters.get(nm, 0) + int(v)
+    return out
+
+
+def weighted_profile(index: LocalIndex, queries: torch.Tensor, radii, weights, squared: bool = False, period=None,
+                     stats: KnnStats | None = None) -> torch.Tensor:
+    """int64 [nq, B], in query order: WP[q, b] = the sum of weights[p] over the points of `index`
+    with dist2(q, p) < cut2_of(radii[b]), strict and cumulative, for B >= 1 ascending radii from
+    one walk of the tree: radius_profile with a weight per point in the place of 1 (with unit
+    weights it equals radius_profile bit for bit, and WP[q, b] is the sum of weights[idx] over
+    row q of radius_neighbors at radii[b]). weights: int64 [n] on the index's device, one per
+    row of the indexed array, negative allowed (data minus randoms), or the PointWeights of
+    prepare_point_weights. The sums are exact, equal to the brute-force oracle bit for bit and
+    independent of the index's order: max|w| * n must be below 2^62, which the host checks (one
+    small device reduction is read) before any kernel runs. Float masses become such weights
+    with fixed_point_weights. radii, squared, period and the limit on NaN *indexed* points as
+    for radius_profile; a query with a NaN or infinite coordinate sums nothing in every column.
+
+    Weights of another dtype, shape or device, weights prepared for another index, an overflow
+    of the bound above and every argument error of radius_profile raise ValueError; an index
+    built in a rotated frame or sorted by line keys is not supported. `stats` receives the
+    radius_* counters of radius_profile (the two walks visit the same nodes). More radii than
+    the kernel's slice width (16) are served in slices, one walk each."""
+    return _weighted("weighted_profile", index, queries, radii, weights, None, squared, period, stats, False)
+
+
+def weighted_pair_sums(index: LocalIndex, queries: torch.Tensor, radii, weights, query_weights=None,
+                       squared: bool = False, period=None, stats: KnnStats | None = None) -> torch.Tensor:
+    """int64 [B] on the index's device: WS[b] = the sum over all queries of query_weights[q] *
+    weighted_profile's WP[q, b], the cumulative weighted pair sums DR(< r_b) of a two-point
+    histogram (shell b holds WS[b] - WS[b - 1]), without ever allocating anything of size nq x
+    B. query_weights: optional int64 [nq] on the index's device, negative allowed; None: all
+    ones. Besides weighted_profile's bound, (sum |weights|) * (sum |query_weights|) (nq without
+    query weights) must be below 2^63, checked on the host: every partial sum is then exact.
+    Integer sums: two runs give the same bits. With unit weights this is pair_counts. Other
+    arguments and errors as for weighted_profile."""
+    return _weighted("weighted_pair_sums", index, queries, radii, weights, query_weights, squared, period, stats,
+                     True)
+
+
+def _weighted_index(what: str, points: torch.Tensor, queries: torch.Tensor, radii, weights, squared: bool,
+                    period) -> LocalIndex | None:
+    """The index of the *_query_* / *_self_* weighted forms; None when there is nothing to index
+    (the radii and the weights are checked all the same)."""
+    index = _profile_index(what, points, queries, radii, squared, period)
+    if index is None:
+        K.int64_weights(what, "weights", weights, 0, points.device)
+    return index
+
+
+def weighted_query_profile(points: torch.Tensor, queries: torch.Tensor, radii, weights: torch.Tensor,
+                           squared: bool = False, period=None, stats: KnnStats | None = None) -> torch.Tensor:
+    """weighted_profile over an index built once from `points` (both float32 [*, 3] on one
+    device), in the points' own frame; weights: int64 [n], one per row of `points`."""
+    index = _weighted_index("weighted_query_profile", points, queries, radii, weights, squared, period)
+    if index is None:
+        return torch.zeros((queries.shape[0], len(radii)), dtype=torch.int64, device=queries.device)
+    return weighted_profile(index, queries, radii, weights, squared=squared, period=period, stats=stats)
+
+
+def weighted_self_profile(points: torch.Tensor, radii, weights: torch.Tensor, squared: bool = False, period=None,
+                          stats: KnnStats | None = None) -> torch.Tensor:
+    """weighted_query_profile with the points as their own queries: every finite point adds its
+    own weight (and that of its exact copies) at every radius > 0."""
+    return weighted_query_profile(points, points, radii, weights, squared=squared, period=period, stats=stats)
+
+
+def weighted_pair_query_sums(points: torch.Tensor, queries: torch.Tensor, radii, weights: torch.Tensor,
+                             query_weights: torch.Tensor | None = None, squared: bool = False, period=None,
+                             stats: KnnStats | None = None) -> torch.Tensor:
+    """weighted_pair_sums over an index built once from `points`, in the points' own frame."""
+    index = _weighted_index("weighted_pair_query_sums", points, queries, radii, weights, squared, period)
+    if index is None:
+        if query_weights is not None:
+            K.int64_weights("weighted_pair_query_sums", "query_weights", query_weights, queries.shape[0],
+                           queries.device)
+        return torch.zeros(len(radii), dtype=torch.int64, device=queries.device)
+    return weighted_pair_sums(index, queries, radii, weights, query_weights=query_weights, squared=squared,
+                              period=period, stats=stats)
+
+
+def weighted_pair_self_sums(points: torch.Tensor, radii, weights: torch.Tensor,
+                            query_weights: torch.Tensor | None = None, squared: bool = False, period=None,
+                            stats: KnnStats | None = None) -> torch.Tensor:
+    """weighted_pair_query_sums with the points as their own queries and, unless query_weights is
+    given, `weights` on both sides: WS[b] = sum of w[p] * w[q] over the ordered pairs with dist2
+    < cut2_of(radii[b]). As pair_self_counts documents, ordered pairs are counted, (p, q) and (q,
+    p) both, and every finite point with itself (w[p]^2, at every radius > 0): the unordered DD
+    is the caller's (WS - WS_at_zero_distance) / 2."""
+    return weighted_pair_query_sums(points, points, radii, weights,
+                                    query_weights=weights if query_weights is None else query_weights,
+                                    squared=squared, period=period, stats=stats)
+
+
+def fixed_point_weights(weights: torch.Tensor, n_terms: int | None = None, bits: int = 62) -> tuple:
+    """(int64 tensor, s): float32 / float64 weights (masses) as exact fixed-point integers w_fix =
+    rint(w * 2^-s), for the weighted_* functions; the physical value of a result is result * 2^s.
+    With A = max|w| <= 2^eA (eA: its frexp exponent) and en = ceil(log2(max(n_terms or len(w),
+    1))), s = eA + en - bits. The scaling is exact in float64 (a power of two) and the rounding is
+    to nearest, ties to even, so the error per weight is at most 2^(s - 1), and |w_fix| <=
+    2^(bits - en): any sum of up to n_terms of them (n_terms: the number of weights that can meet
+    in one sum, the whole catalogue's size when it is converted in pieces) has sum |w_fix| <=
+    2^bits. bits = 62 (the default) meets weighted_profile's bound.
+
+    Pair sums multiply the two sides: weighted_pair_sums needs (sum |w|) * (sum |wq|) < 2^63, so
+    the caller splits the 62 bits between the point weights and the query weights, e.g. bits=31
+    for each (results then carry the quantum 2^(s_points + s_queries)); the library does not
+    hide that choice. Unit query weights (query_weights=None) cost ceil(log2(nq)) bits.
+
+    All-zero (or no) weights give zeros and s = 0. A NaN or infinite weight, a tensor that is
+    not 1-D float32 / float64, n_terms < 1 or bits outside 1 .. 62 raise ValueError."""
+    what = "fixed_point_weights"
+    if not isinstance(weights, torch.Tensor) or weights.dtype not in (torch.float32, torch.float64) \
+            or weights.dim() != 1:
+        got = f"{weights.dtype} {tuple(weights.shape)}" if isinstance(weights, torch.Tensor) \
+            else type(weights).__name__
+        raise ValueError(f"{what}: weights must be a float32 / float64 [n] tensor (got {got})")
+    if isinstance(bits, bool) or not isinstance(bits, int) or not 1 <= bits <= 62:
+        raise ValueError(f"{what}: bits must be an integer in 1 .. 62 (got {bits!r})")
+    if n_terms is not None and (isinstance(n_terms, bool) or not isinstance(n_terms, int) or n_terms < 1):
+        raise ValueError(f"{what}: n_terms must be an integer >= 1 (got {n_terms!r})")
+    w = weights.double()
+    top = float(w.abs().max()) if w.numel() else 0.0
+    if not math.isfinite(top):  # (a NaN propagates through max)
+        raise ValueError(f"{what}: weights must be finite (no NaN, no inf)")
+    if top == 0.0:
+        return torch.zeros(w.shape, dtype=torch.int64, device=w.device), 0
+    e_a = math.frexp(top)[1]
+    e_n = (max(n_terms or w.shape[0], 1) - 1).bit_length()
+    s = e_a + e_n - bits
+    half = (-s) // 2  # two exact steps: 2^-s itself may lie outside float64's range
+    scaled = (w * math.ldexp(1.0, half)) * math.ldexp(1.0, -s - half)
+    return torch.round(scaled).to(torch.int64), s
+
+
 def _no_period(what: str, period) -> None:
     if period is not None:
         raise ValueError(f"{what}: a period is not supported for per-point radii")

@@ -1158,6 +1158,123 @@ def pair_counts_gpu(tree: tuple, qsorted: torch.Tensor, nq: int, cut2s, out_perm
     return sums
 
 
+# --------------------------------------------------------------------------- weighted radius profiles
+def int64_weights(what: str, name: str, w, count: int, device: torch.device | None = None) -> torch.Tensor:
+    """The int64 [count] weight tensor `name` of the function `what`, checked and contiguous (also
+    knn_engine's check); device: where it must live (None: anywhere). ValueError otherwise."""
+    if not isinstance(w, torch.Tensor) or w.dtype != torch.int64 or w.dim() != 1 or w.shape[0] != count:
+        got = f"{w.dtype} {tuple(w.shape)}" if isinstance(w, torch.Tensor) else type(w).__name__
+        raise ValueError(f"{what}: {name} must be an int64 [{count}] tensor (got {got})")
+    if device is not None and w.device != device:
+        raise ValueError(f"{what}: {name} on {w.device}, the index on {device}")
+    return w.contiguous()
+
+
+def weighted_profile_cpu(points: torch.Tensor, queries: torch.Tensor, cut2s, weights: torch.Tensor,
+                         period=None) -> torch.Tensor:
+    """CPU oracle (brute force over all pairs): int64 [nq, B], column b = the sum of weights[i]
+    over the rows i of `points` with dist2 < cut2s[b] (strict; with `period` the minimum-image
+    distance), summed per shell and then prefix-summed. weights: int64 [n], one per row of
+    `points`, negative allowed; the sums wrap in 64 bits (exact when sum |w| < 2^63). With unit
+    weights this is radius_profile_cpu."""
+    c = _profile_cut2s("weighted_profile_cpu", cut2s)
+    per = None if period is None else check_period("weighted_profile_cpu", period)
+    pts = points.contiguous().float().cpu()
+    q = queries.contiguous().float().cpu()
+    w = int64_weights("weighted_profile_cpu", "weights", weights, pts.shape[0]).cpu()
+    out = torch.empty((q.shape[0], c.shape[0]), dtype=torch.int64)
+    _native.host().lsk_cpu_weighted_profile(_ptr(pts), pts.shape[0], _ptr(q), q.shape[0], _ptr(c), c.shape[0],
+                                            None if per is None else _period_c(per), _ptr(w), _ptr(out),
+                                            _nthreads())
+    return out
+
+
+def weighted_pair_sums_cpu(points: torch.Tensor, queries: torch.Tensor, cut2s, weights: torch.Tensor,
+                           period=None, query_weights: torch.Tensor | None = None) -> torch.Tensor:
+    """CPU oracle of the weighted pair sums: int64 [B], the sum over the queries of
+    query_weights[q] (int64 [nq]; None: 1) times row q of weighted_profile_cpu."""
+    prof = weighted_profile_cpu(points, queries, cut2s, weights, period)
+    if query_weights is not None:
+        wq = int64_weights("weighted_pair_sums_cpu", "query_weights", query_weights, prof.shape[0]).cpu()
+        prof = prof * wq[:, None]
+    return prof.sum(0, dtype=torch.int64)
+
+
+def weighted_profile_bins() -> int:
+    """Cutoffs per launch of weighted_profile.hip (kWeightedBins); longer lists go in slices."""
+    return int(_native.hip().lsk_hip_weighted_profile_bins())
+
+
+def _weighted_args(what: str, tree: tuple, wsorted: torch.Tensor, wpre: torch.Tensor) -> None:
+    n, dev = tree[3], tree[0].device
+    for name, t, count in (("wsorted", wsorted, n), ("wpre", wpre, n + 1)):
+        if t.dtype != torch.int64 or t.dim() != 1 or t.shape[0] != count or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{what}: {name} must be a contiguous int64 [{count}] tensor on the tree's device")
+
+
+def weighted_profile_gpu(tree: tuple, qsorted: torch.Tensor, nq: int, cut2s, out_perm: torch.Tensor,
+                         wsorted: torch.Tensor, wpre: torch.Tensor,
+                         period: tuple[float, float, float] | None = None,
+                         stats: torch.Tensor | None = None) -> torch.Tensor:
+    """The weighted radius profile (weighted_profile.hip) on the current stream: int64 [nq, B] in
+    query order, column b = the sum of the weights of the points with dist2 < cut2s[b], from one
+    walk per slice of up to weighted_profile_bins() cutoffs. wsorted: int64 [n], the weights in
+    the tree's curve order; wpre: int64 [n + 1], their exclusive prefix sum. The caller
+    guarantees max|w| * n < 2^62. Everything else as for radius_profile_gpu."""
+    c = _profile_cut2s("weighted_profile_gpu", cut2s)
+    tv = _walk_view("weighted_profile_gpu", tree, qsorted, nq, out_perm)
+    dev = tree[0].device
+    _profile_stats("weighted_profile_gpu", stats, period, dev)
+    _weighted_args("weighted_profile_gpu", tree, wsorted, wpre)
+    nb = c.shape[0]
+    out = torch.empty((nq, nb), dtype=torch.int64, device=dev)
+    cdev = c.to(dev)
+    per = None if period is None else _period_c(period)
+    lib = _native.hip()
+    width = int(lib.lsk_hip_weighted_profile_bins())
+    for col0 in range(0, nb, width):
+        m = min(width, nb - col0)
+        check(lib.lsk_hip_weighted_profile(C.byref(tv), _ptr(qsorted), int(nq), cdev.data_ptr() + 4 * col0, m, per,
+                                           _ptr(out_perm), _ptr(wsorted), _ptr(wpre), _ptr(out), nb, col0,
+                                           _ptr(stats), _stream(tree[0])),
+              "weighted_profile")
+    return out
+
+
+def weighted_pair_sums_gpu(tree: tuple, qsorted: torch.Tensor, nq: int, cut2s, out_perm: torch.Tensor,
+                           wsorted: torch.Tensor, wpre: torch.Tensor, query_weights: torch.Tensor | None = None,
+                           period: tuple[float, float, float] | None = None,
+                           stats: torch.Tensor | None = None) -> torch.Tensor:
+    """The weighted pair sums (weighted_profile.hip, sum mode) on the current stream: int64 [B] on
+    the tree's device, the sum over the queries of query_weights[q] (int64 [nq] in query order;
+    None: 1) times row q of weighted_profile_gpu, without its [nq, B] array. The caller
+    guarantees (sum |w|) * (sum |query_weights|) < 2^63. Arguments as for weighted_profile_gpu."""
+    c = _profile_cut2s("weighted_pair_sums_gpu", cut2s)
+    tv = _walk_view("weighted_pair_sums_gpu", tree, qsorted, nq, out_perm)
+    dev = tree[0].device
+    _profile_stats("weighted_pair_sums_gpu", stats, period, dev)
+    _weighted_args("weighted_pair_sums_gpu", tree, wsorted, wpre)
+    wq = query_weights
+    if wq is not None and (wq.dtype != torch.int64 or wq.dim() != 1 or wq.shape[0] != nq or not wq.is_contiguous()
+                           or wq.device != dev):
+        raise ValueError(f"weighted_pair_sums_gpu: query_weights must be a contiguous int64 [{nq}] tensor on the "
+                         f"tree's device")
+    nb = c.shape[0]
+    sums = torch.zeros(nb, dtype=torch.int64, device=dev)
+    cdev = c.to(dev)
+    per = None if period is None else _period_c(period)
+    lib = _native.hip()
+    width = int(lib.lsk_hip_weighted_profile_bins())
+    ws = torch.empty(int(lib.lsk_hip_weighted_pair_sums_ws_bytes(int(nq))) // 8, dtype=torch.int64, device=dev)
+    for col0 in range(0, nb, width):
+        m = min(width, nb - col0)
+        check(lib.lsk_hip_weighted_pair_sums(C.byref(tv), _ptr(qsorted), int(nq), cdev.data_ptr() + 4 * col0, m, per,
+                                             _ptr(out_perm), _ptr(wsorted), _ptr(wpre), _ptr(wq), _ptr(ws),
+                                             _ptr(sums), col0, _ptr(stats), _stream(tree[0])),
+              "weighted_pair_sums")
+    return sums
+
+
 # --------------------------------------------------------------------------- periodic k-NN
 def kth_periodic_cpu(points: torch.Tensor, queries: torch.Tensor, k: int, cut2: float, period) -> torch.Tensor:
     """CPU oracle (brute force): kth_cpu with the periodic squared distance of

@@ -5,7 +5,7 @@
                                    [--radii scalar|query-equal|query-loguniform|query-kth|point-kth]
                                    [--period L | Lx,Ly,Lz]
     python scripts/radius_bench.py --profile B [-r R] [--self-queries] [--points ..] [--queries ..] [--mean ..]
-                                   [--steps ..] [--warmup ..] [--period ..]
+                                   [--steps ..] [--warmup ..] [--period ..] [--weights]
 
 Uniform points in the unit cube and uniform queries from another seed; the radius is the one
 whose ball holds --mean points at the data's density (queries near the faces see fewer, so
@@ -34,6 +34,16 @@ timed alternately as above: one radius_profile call, one pair_counts call, and t
 radius_counts calls they replace. The JSON carries the three medians and the radius_* counters
 of each (one extra, untimed call with stats); the profile's columns are compared with the B
 counts, and its column sums with the pair counts, before anything is reported.
+
+--profile B --weights: the weighted profile. int64 weights drawn from +-2^15 on the points, timed
+alternately in one process: one weighted_profile call and one weighted_pair_sums call (weights
+prepared once, outside the timed region); one radius_profile call, the same walk with 32-bit
+counters and no weight traffic; and the route without the weighted kernels, at the largest radius
+only: radius_neighbors(sort=False) in query chunks that respect max_pairs, a gather of the weights
+by id and a segment sum in torch. The JSON carries the medians and the radius_* counters of the
+weighted and the unweighted walk (equal when B fits one slice of both kernels: the walks are the
+same); the weighted profile's last column is compared with the pair-list route, its column sums
+with the pair sums, before anything is reported.
 """
 from __future__ import annotations
 
@@ -102,6 +112,79 @@ def profile_bench(a, p: torch.Tensor, q: torch.Tensor, r: float, per: dict) -> i
     return 0 if same_columns and same_sums else 1
 
 
+def pair_list_sums(index, q: torch.Tensor, r: float, w: torch.Tensor, per: dict, chunk: int) -> torch.Tensor:
+    """Sum of w over every query's neighbours within r by way of the pair lists: int64 [nq]."""
+    out = torch.empty(q.shape[0], dtype=torch.int64, device=q.device)
+    for a in range(0, q.shape[0], chunk):
+        offsets, idx, _ = E.radius_neighbors(index, q[a:a + chunk], r, sort=False, **per)
+        run = torch.zeros(idx.shape[0] + 1, dtype=torch.int64, device=q.device)
+        torch.cumsum(w[idx.long()], 0, out=run[1:])
+        out[a:a + chunk] = run[offsets[1:]] - run[offsets[:-1]]
+    return out
+
+
+def weighted_bench(a, p: torch.Tensor, q: torch.Tensor, r: float, per: dict) -> int:
+    """--profile B --weights: weighted_profile / weighted_pair_sums, radius_profile, the pair-list route."""
+    B = a.profile
+    radii = [r * 8.0 ** (-(B - 1 - b) / max(B - 1, 1)) for b in range(B)]
+    radii[-1] = r
+    index = E.build_index(p)
+    w = torch.randint(-(1 << 15), (1 << 15) + 1, (p.shape[0],), dtype=torch.int64, device=p.device,
+                      generator=torch.Generator(device=p.device).manual_seed(5))
+    pw = E.prepare_point_weights(index, w)
+    # query chunks of the pair-list route: at most 2^27 pairs expected in each (max_pairs is 2^28)
+    chunk = max(1, int((1 << 27) / max(a.mean, 1)))
+    out = {}
+    cases = {
+        "weighted_profile": lambda **kw: out.__setitem__(
+            "wprofile", E.weighted_profile(index, q, radii, pw, **per, **kw)),
+        "weighted_pairs": lambda **kw: out.__setitem__(
+            "wpairs", E.weighted_pair_sums(index, q, radii, pw, **per, **kw)),
+        "profile": lambda **kw: out.__setitem__("profile", E.radius_profile(index, q, radii, **per, **kw)),
+        "pair_list": lambda: out.__setitem__("list", pair_list_sums(index, q, r, w, per, chunk)),
+    }
+    times = {name: [] for name in cases}
+    for step in range(a.warmup + a.steps):
+        for name, fn in cases.items():
+            out.clear()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            if step >= a.warmup:
+                times[name].append(time.perf_counter() - t0)
+    med = {name: statistics.median(ts) for name, ts in times.items()}
+    counters = {}
+    out.clear()
+    for name, fn in cases.items():
+        if name == "pair_list":
+            fn()
+            continue
+        st = E.KnnStats()
+        fn(stats=st)
+        counters[name] = dict(st.counters)
+    wprof, wpairs = out["wprofile"], out["wpairs"]
+    same_list = bool(torch.equal(wprof[:, -1], out["list"]))
+    same_sums = bool(torch.equal(wprof.sum(0, dtype=torch.int64), wpairs))
+    rec = {
+        "points": p.shape[0], "queries": q.shape[0], "self_queries": bool(a.self_queries), "profile": B,
+        "weights": "int64 +-2^15", "radii": radii, "steps": a.steps, "warmup": a.warmup,
+        "mean_count_at_r": float(out["profile"][:, -1].sum(dtype=torch.int64)) / q.shape[0],
+        "weighted_profile_s": med["weighted_profile"], "weighted_pairs_s": med["weighted_pairs"],
+        "profile_s": med["profile"], "pair_list_s": med["pair_list"], "pair_list_chunk": chunk,
+        "weighted_over_profile": med["weighted_profile"] / med["profile"],
+        "pair_list_over_weighted": med["pair_list"] / med["weighted_profile"],
+        "spread": {name: [min(ts), max(ts)] for name, ts in times.items()},
+        "counters": counters, "counters_equal": counters["weighted_profile"] == counters["profile"],
+        "wpairs": wpairs.tolist(),
+        "last_column_equals_pair_list": same_list, "sums_equal_pairs": same_sums,
+    }
+    if a.period is not None:
+        rec["period"] = list(a.period)
+    print(json.dumps(rec), flush=True)
+    return 0 if same_list and same_sums else 1
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=float, default=1e7)
@@ -115,10 +198,11 @@ def main() -> int:
     ap.add_argument("--profile", type=int, default=0, metavar="B", help="time the radius profile at B radii instead")
     ap.add_argument("-r", dest="radius", type=float, default=None, help="--profile: the largest radius")
     ap.add_argument("--self-queries", action="store_true", help="--profile: the points are their own queries")
+    ap.add_argument("--weights", action="store_true", help="--profile: the weighted profile and its alternatives")
     add_period_option(ap)
     a = ap.parse_args()
-    if a.profile < 0 or (a.profile == 0 and (a.radius is not None or a.self_queries)):
-        ap.error("--profile B needs B >= 1; -r and --self-queries belong to it")
+    if a.profile < 0 or (a.profile == 0 and (a.radius is not None or a.self_queries or a.weights)):
+        ap.error("--profile B needs B >= 1; -r, --self-queries and --weights belong to it")
     if a.period is not None and a.radii == "point-kth":
         ap.error("--period is not supported with --radii point-kth")
     per = {} if a.period is None else {"period": a.period}  # (none: the calls without the keyword)
@@ -131,7 +215,8 @@ def main() -> int:
     q = torch.rand((nq, 3), generator=torch.Generator(device=dev).manual_seed(2), device=dev)
     r = (k / (n * 4.0 / 3.0 * math.pi)) ** (1.0 / 3.0)
     if a.profile:
-        return profile_bench(a, p, p if a.self_queries else q, a.radius if a.radius is not None else r, per)
+        bench = weighted_bench if a.weights else profile_bench
+        return bench(a, p, p if a.self_queries else q, a.radius if a.radius is not None else r, per)
     index = E.build_index(p, grid=True)
     E.bucket_keys(index)
     cfg = E.KnnConfig(k=k)
