@@ -57,7 +57,7 @@ using lsk::fbits;
 #define LSK_GRID_MINW 6
 #endif
 #ifndef LSK_GRID_BATCH
-#define LSK_GRID_BATCH 8  // candidates per scalar-load batch of the cell stream (4 or 8; 8: 1B stream 952.6 -> 941.9-943.3 ms, profiles/r5_kernel_ab)
+#define LSK_GRID_BATCH 8  // candidates per scalar-load batch of the cell stream (8 against 4: 1B stream 952.6 -> 941.9-943.3 ms, profiles/r5_kernel_ab)
 #endif
 #ifndef LSK_GRID_WPB
 // waves per workgroup: 1 (1e8 k=100 at 6 waves/SIMD: 77.0 ms; 2: 78.1; 4: 79.6,
@@ -541,46 +541,108 @@ __device__ __forceinline__ CellLoad fetch_cell(const GridCtx &G, uint32_t x, uin
   return CellLoad{v.x, v.y, v.z};
 }
 
-template <int MODE>
-__device__ __forceinline__ void count_batch(GridCtx &G) {
-  G.evals += (uint32_t)LSK_GRID_BATCH;
-#ifdef LSK_GRID_PROFILE
-  G.ev_mode[MODE] += (uint32_t)LSK_GRID_BATCH;
-#endif
-}
-
-// The last batch of a segment: slots past its end count nowhere.
-template <int MODE>
-__device__ __forceinline__ void eval4_tail(Lane &s, GridCtx &G, const Batch &b, uint32_t left) {
-  const uint32_t u0 = fbits(lsk::dist2(s.qx - b.x0, s.qy - b.y0, s.qz - b.z0));
-  const uint32_t u1 = left > 1u ? fbits(lsk::dist2(s.qx - b.x1, s.qy - b.y1, s.qz - b.z1)) : ~0u;
-  const uint32_t u2 = left > 2u ? fbits(lsk::dist2(s.qx - b.x2, s.qy - b.y2, s.qz - b.z2)) : ~0u;
-  update4<MODE>(s, G, u0, u1, u2, ~0u);
-}
-
-#if LSK_GRID_BATCH == 8
+// ---- the cell stream: 8 candidates per scalar-load batch (24 dwords, x16 + x8)
+static_assert(LSK_GRID_BATCH == 8, "the cell stream is written for 8-candidate batches");
 struct Batch8 {
   Batch a, b;
 };
-__device__ __forceinline__ Batch8 load_batch8(lsk::cfloat_p P, uint32_t i) {
-  const lsk::cfloat_p p = P + 3ull * (uint64_t)i;
+__device__ __forceinline__ Batch8 load_batch8(lsk::cfloat_p p) {
   return Batch8{Batch{p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], p[9], p[10], p[11]},
                 Batch{p[12], p[13], p[14], p[15], p[16], p[17], p[18], p[19], p[20], p[21], p[22], p[23]}};
 }
-template <int MODE>
-__device__ __forceinline__ void eval8(Lane &s, GridCtx &G, const Batch8 &b, uint32_t left) {
-  if (left >= 4u) eval4<MODE>(s, G, b.a); else eval4_tail<MODE>(s, G, b.a, left);
-  if (left >= 8u) eval4<MODE>(s, G, b.b); else if (left > 4u) eval4_tail<MODE>(s, G, b.b, left - 4u);
+// d² bits of candidate T of a batch
+template <int T>
+__device__ __forceinline__ uint32_t cand8(const Lane &s, const Batch8 &b8) {
+  const Batch &b = T < 4 ? b8.a : b8.b;
+  constexpr int t = T & 3;
+  const float x = t == 0 ? b.x0 : t == 1 ? b.x1 : t == 2 ? b.x2 : b.x3;
+  const float y = t == 0 ? b.y0 : t == 1 ? b.y1 : t == 2 ? b.y2 : b.y3;
+  const float z = t == 0 ? b.z0 : t == 1 ? b.z1 : t == 2 ? b.z2 : b.z3;
+  return fbits(lsk::dist2(s.qx - x, s.qy - y, s.qz - z));
 }
-#endif
+// the branch-free histogram add of one value (see update4; the stream counts its adds per
+// segment, not here)
+__device__ __forceinline__ void hist_add1(const Lane &s, uint32_t u) {
+  lds_add(hist_row_addr(u, s.lo_b, s.chi, s.shift, s.hbase), s.inc);
+}
+// collect pass: the band's values of one batch into the lane's pool; one wave vote per
+// batch (update4: one per 4)
+__device__ __forceinline__ void collect8(Lane &s, GridCtx &G, const uint32_t (&u)[8]) {
+  const uint32_t bl = s.band_lo, bw = s.band_w;
+  bool any = false;
+#pragma unroll
+  for (int t = 0; t < 8; t++) any = any || (u[t] - bl < bw);
+  if (!__ballot(any)) return;
+#pragma unroll
+  for (int t = 0; t < 8; t++) {
+    if (u[t] - bl < bw) {
+      if (s.ccnt < s.bc) G.pool[s.coff + s.ccnt] = u[t];
+      s.ccnt++;
+    }
+  }
+}
+// A full batch: no end-of-segment logic at all.
+template <int MODE>
+__device__ __forceinline__ void stream8(Lane &s, GridCtx &G, const Batch8 &b) {
+  const uint32_t u[8] = {cand8<0>(s, b), cand8<1>(s, b), cand8<2>(s, b), cand8<3>(s, b),
+                         cand8<4>(s, b), cand8<5>(s, b), cand8<6>(s, b), cand8<7>(s, b)};
+  if (MODE == MODE_HIST) {
+#pragma unroll
+    for (int t = 0; t < 8; t++) hist_add1(s, u[t]);
+  } else {
+    collect8(s, G, u);
+  }
+}
+// The last batch of a segment, `left` (1..8) candidates: the slots past the end are not
+// evaluated at all (histogram: they add nowhere — the segment's adds are counted as its
+// length; collect: they keep ~0u, outside every band). Four wave-uniform compares: the
+// half, then plain if-thens (no select per slot).
+template <int MODE>
+__device__ __forceinline__ void stream8_tail(Lane &s, GridCtx &G, const Batch8 &b, uint32_t left) {
+  uint32_t u[8] = {~0u, ~0u, ~0u, ~0u, ~0u, ~0u, ~0u, ~0u};
+  auto take = [&](uint32_t &dst, uint32_t v) {
+    if (MODE == MODE_HIST) hist_add1(s, v); else dst = v;
+  };
+  take(u[0], cand8<0>(s, b));
+  if (left > 4u) {
+    take(u[1], cand8<1>(s, b));
+    take(u[2], cand8<2>(s, b));
+    take(u[3], cand8<3>(s, b));
+    take(u[4], cand8<4>(s, b));
+    if (left > 5u) take(u[5], cand8<5>(s, b));
+    if (left > 6u) take(u[6], cand8<6>(s, b));
+    if (left > 7u) take(u[7], cand8<7>(s, b));
+  } else {
+    if (left > 1u) take(u[1], cand8<1>(s, b));
+    if (left > 2u) take(u[2], cand8<2>(s, b));
+    if (left > 3u) take(u[3], cand8<3>(s, b));
+  }
+  if (MODE == MODE_COLLECT) collect8(s, G, u);
+}
 
-// The candidates of one cell as ONE stream over its needed runs of grandchildren, 4 per
+// The candidates of one cell as ONE stream over its needed runs of grandchildren, 8 per
 // batch. Slots are in memory order, so a run of needed (or empty) slots is one
 // contiguous segment of the sorted array. The next batch's scalar loads — the next
 // segment's first batch at a segment end — are issued before the current batch is
-// computed, so short segments do not each pay a cold load latency. Unrolled by two with
+// computed, so short segments do not each pay a cold load latency. Two steps per trip with
 // A / B batch registers (a loop-carried copy would make the compiler wait for the prefetch
 // right after issuing it).
+//
+// The scalar unit is the tighter limit of this kernel (one per CU, shared by the four
+// SIMDs; profiles/grid_scalar), so the state of the stream is what one step needs and no
+// more: a cursor `p` (the address of the current batch: + 96 bytes per batch, computed from
+// the point index once per segment) and `left`, the candidates from p to the segment's
+// end. A batch inside a segment costs one compare of `left`, the two updates and the
+// loads; everything else (the next segment, the counters, the long-segment check) happens
+// once per segment:
+//   * adds (histogram adds per lane, what hist_fold subtracts the clamp row from) grows by
+//     a segment's length and evals by its length rounded up to whole batches, when the
+//     segment becomes current — both are exact whenever a fold can happen;
+//   * a segment of more than kSegCheck candidates is streamed in pieces of kSegCheck: at
+//     the end of a piece the bounds are folded and shrunk and, once every lane's bound has
+//     closed (k exact copies: the k-th is 0), the rest of the cell cannot count. A piece
+//     holds at most kSegCheck adds and a cell at most 32 segments (two runs are separated
+//     by an unneeded slot), so the clamp row's 16-bit counters cannot wrap between folds.
 //   need: needed non-empty slots; free: needed or empty slots (runs of `free` that hold
 //   a needed slot are the segments).
 template <int MODE>
@@ -588,79 +650,86 @@ __device__ __forceinline__ void process_cell_stream(Lane &s, GridCtx &G, const C
                                                     uint64_t free) {
   const lsk::cfloat_p P = lsk::as_const(G.pts);
   // pops the next segment: [start of its first needed slot, end of its last needed slot)
-  auto pop = [&](uint32_t &a, uint32_t &b) {
-    const uint32_t t0 = (uint32_t)__builtin_ctzll(need);
-    const uint64_t after = ~free >> t0;  // first slot past the run of free slots
-    const uint32_t len = after ? (uint32_t)__builtin_ctzll(after) : 64u - t0;
-    const uint64_t run = (len >= 64u ? ~0ull : ((1ull << len) - 1ull)) << t0;
+  auto pop = [&](lsk::cfloat_p &q, uint32_t &len) {
+    // the run of free slots from the lowest needed one: adding that slot's bit to `free`
+    // carries through the run and clears it
+    const uint64_t low = need & (0ull - need);
+    const uint64_t run = free & ~(free + low);
     const uint64_t in = need & run;
+    const uint32_t t0 = (uint32_t)__builtin_ctzll(low);
     const uint32_t t1 = 63u - (uint32_t)__builtin_clzll(in);
     need &= ~run;
-    a = lsk::uniform((uint32_t)__builtin_amdgcn_readlane((int)c.a, (int)t0));
-    b = lsk::uniform((uint32_t)__builtin_amdgcn_readlane((int)c.e, (int)t1));
+    const uint32_t a = lsk::uniform((uint32_t)__builtin_amdgcn_readlane((int)c.a, (int)t0));
+    const uint32_t b = lsk::uniform((uint32_t)__builtin_amdgcn_readlane((int)c.e, (int)t1));
+    q = P + 3ull * (uint64_t)a;
+    len = b - a;
     G.segs++;
   };
-  uint32_t i, e;
-  pop(i, e);
-  uint32_t chk = i + kSegCheck;
-  // position after batch i of [.., e): next batch of the segment, else the next segment
-  auto advance = [&](uint32_t &ni, uint32_t &ne) -> bool {
-    ni = i + (uint32_t)LSK_GRID_BATCH;
-    ne = e;
-    if (ni < e) return true;
-    if (!need) {
-      ni = i;  // (a dummy reload of the current batch: in flight, unused)
-      return false;
+  // a segment (or piece) becomes current
+  auto enter = [&](uint32_t len) {
+    if (MODE == MODE_HIST) G.adds += len;
+    const uint32_t ev = (len + 7u) & ~7u;
+    G.evals += ev;
+#ifdef LSK_GRID_PROFILE
+    G.ev_mode[MODE] += ev;
+#endif
+  };
+  lsk::cfloat_p p;
+  uint32_t left, rest;  // candidates of the current piece from p; of the segment after the piece
+  {
+    uint32_t len;
+    pop(p, len);
+    left = min(len, kSegCheck);
+    rest = len - left;
+  }
+  enter(left);
+  // One batch: X holds it (in flight), Y takes the next one. False at the end of the
+  // stream or of a piece (rest != 0) — the steps themselves hold wave-uniform branches only.
+  auto step = [&](const Batch8 &X, Batch8 &Y) -> bool {
+    if (left > 8u) {  // inside the segment: a full batch, and the next one follows it
+      p += 24;
+      left -= 8u;
+      __builtin_amdgcn_s_waitcnt(kWaitLgkm0);
+      Y = load_batch8(p);
+      __builtin_amdgcn_sched_barrier(0);
+      stream8<MODE>(s, G, X);
+      return true;
     }
-    pop(ni, ne);
+    // the last batch of the segment: the next segment's first batch is fetched under it
+    const bool more = rest == 0u && need != 0ull;
+    lsk::cfloat_p np = p;
+    uint32_t nlen = 0;
+    if (more) pop(np, nlen);
+    __builtin_amdgcn_s_waitcnt(kWaitLgkm0);
+    if (more) Y = load_batch8(np);
+    __builtin_amdgcn_sched_barrier(0);
+    stream8_tail<MODE>(s, G, X, left);
+    if (!more) return false;
+    p = np;
+    left = min(nlen, kSegCheck);
+    rest = nlen - left;
+    enter(left);
     return true;
   };
-#if LSK_GRID_BATCH == 8
-  Batch8 A = load_batch8(P, i);
-#else
-  Batch A = load_batch(P, i);
-#endif
   for (;;) {
-    uint32_t ni, ne;
-    bool more = advance(ni, ne);
-    __builtin_amdgcn_s_waitcnt(kWaitLgkm0);
-#if LSK_GRID_BATCH == 8
-    Batch8 B = load_batch8(P, ni);
-    __builtin_amdgcn_sched_barrier(0);
-    eval8<MODE>(s, G, A, e - i);
-#else
-    Batch B = load_batch(P, ni);
-    __builtin_amdgcn_sched_barrier(0);
-    if (e - i >= 4u) eval4<MODE>(s, G, A); else eval4_tail<MODE>(s, G, A, e - i);
-#endif
-    count_batch<MODE>(G);
-    if (!more) break;
-    i = ni;
-    e = ne;
-    more = advance(ni, ne);
-    __builtin_amdgcn_s_waitcnt(kWaitLgkm0);
-#if LSK_GRID_BATCH == 8
-    A = load_batch8(P, ni);
-    __builtin_amdgcn_sched_barrier(0);
-    eval8<MODE>(s, G, B, e - i);
-#else
-    A = load_batch(P, ni);
-    __builtin_amdgcn_sched_barrier(0);
-    if (e - i >= 4u) eval4<MODE>(s, G, B); else eval4_tail<MODE>(s, G, B, e - i);
-#endif
-    count_batch<MODE>(G);
-    if (!more) break;
-    i = ni;
-    e = ne;
-    if (MODE == MODE_HIST && i >= chk) {
-      // long stream (a crowded cell): once every lane's bound has closed (k exact copies:
-      // the k-th is 0) the rest of it cannot count
-      chk = i + kSegCheck;
+    Batch8 A = load_batch8(p), B;  // (B: written by the first step before any use)
+    for (;;) {
+      if (!step(A, B)) break;
+      if (!step(B, A)) break;
+    }
+    if (rest == 0u) break;
+    // between two pieces of a long segment (a crowded sub-cell; the next piece starts cold)
+    if (MODE == MODE_HIST) {
       shrink_all<MODE>(s, G);
       if (!__ballot(s.state == ST_HIST && s.hi_b > 0u)) break;
     }
+    p += 24;
+    left = min(rest, kSegCheck);
+    rest -= left;
+    enter(left);
   }
 }
+
 
 // Unrolled by two with separate A / B batch registers: a loop-carried copy of the batch
 // would make the compiler wait for the prefetch right after issuing it.
@@ -764,6 +833,8 @@ constexpr uint32_t kScanAll = 1u << 16;
 template <int MODE>
 __device__ bool grid_pass_impl(Lane &s, GridCtx &G, uint32_t n);
 
+// Per-row candidate streams (round 6, measured and killed: 96.7 vs 74.3 ms at 1e8,
+// profiles/r6_rowq): kept beside the other rejected experiments, compiled in only on demand.
 #ifndef LSK_GRID_ROWQ
 #define LSK_GRID_ROWQ 0
 #endif
@@ -771,249 +842,7 @@ __device__ bool grid_pass_impl(Lane &s, GridCtx &G, uint32_t n);
 #define LSK_ROWQ_LOW 1  // a row with at most this many queued segments asks for the next cell
 #endif
 #if LSK_GRID_ROWQ
-// ------------------------------------------------------------------ per-row candidate streams
-// Each 16-query row streams ITS OWN candidates (round 6; the SGPR form above streams the
-// union of the four rows' needs to all 64 lanes). Cells are still taken nearest first by
-// the wave, tested per row (process_cell's row boxes and radii), and each row's runs of
-// needed grandchildren ("segments") are appended to that row's queue; a step takes the
-// next 16 candidates of every row at once: lane j of row r loads candidate j of its row
-// (one vector load, issued a step ahead) and the row's 16 lanes read it with a DPP
-// row_newbcast folded into the distance's v_subrev_f32_dpp. Rows consume their queues
-// independently across cells, so a row never pays for another row's candidates.
-//
-// Queue of row r: lanes 16r + t of (qa, qe) hold its t-th segment [qa, qe) of the sorted
-// points (t = 0: the head, partly consumed: qa advances); qn = segments queued (the same
-// in every lane of the row). A full queue (16) blocks the next cell; within one cell, the
-// segments past the 16th are merged into the 16th (the slots between them are unneeded by
-// that row and lie in the same cell: extra candidates, never a repeated one).
-template <int J>
-__device__ __forceinline__ float rowb(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x150 + J, 0xf, 0xf, false));
-}
-template <int J>
-__device__ __forceinline__ uint32_t rowb_u(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x150 + J, 0xf, 0xf, false);
-}
-// lane j of each row <- lane j + 1 (lane 15 <- 0)
-__device__ __forceinline__ uint32_t row_shl1(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x101, 0xf, 0xf, true);
-}
-
-struct RowQ {
-  uint32_t qa, qe, qn;
-};
-struct RowPts {
-  float x, y, z;
-};
-
-// The next (up to) 16 candidates of this lane's row: lane j loads candidate j (padding:
-// the +inf point, d² = +inf, at or past every range top and collect band). At most one
-// segment boundary per step; a consumed head segment is popped (the queue shifts down).
-__device__ __forceinline__ RowPts rowq_take(RowQ &Q, GridCtx &G) {
-  const uint32_t j = (uint32_t)G.lane & 15u;
-  const uint32_t a0 = rowb_u<0>(Q.qa), e0 = rowb_u<0>(Q.qe), a1 = rowb_u<1>(Q.qa), e1 = rowb_u<1>(Q.qe);
-  const uint32_t l0 = e0 - a0, l1 = e1 - a1;
-  const uint32_t took = min(l0 + l1, 16u);
-#ifdef LSK_ROWQ_STATS
-  G.rq_steps++;
-  G.rq_took += (uint32_t)__builtin_amdgcn_readlane((int)took, 0) + (uint32_t)__builtin_amdgcn_readlane((int)took, 16) +
-               (uint32_t)__builtin_amdgcn_readlane((int)took, 32) + (uint32_t)__builtin_amdgcn_readlane((int)took, 48);
-#endif
-  const uint32_t idx = j < l0 ? a0 + j : a1 + (j - l0);
-  const float *p = j < took ? G.pts + 3ull * idx : G.inf4;
-  const RowPts r{p[0], p[1], p[2]};
-  const bool pop = took >= l0 && Q.qn > 0u;
-  const uint32_t sa = row_shl1(Q.qa), se = row_shl1(Q.qe);
-  Q.qa = pop ? sa : Q.qa;
-  Q.qe = pop ? se : Q.qe;
-  if (j == 0u) Q.qa = pop ? a1 + (took - l0) : a0 + took;
-  Q.qn -= pop ? 1u : 0u;
-  return r;
-}
-
-template <int J>
-__device__ __forceinline__ uint32_t rcand(const Lane &s, const RowPts &p) {
-  return fbits(lsk::dist2(s.qx - rowb<J>(p.x), s.qy - rowb<J>(p.y), s.qz - rowb<J>(p.z)));
-}
-
-template <int MODE>
-__device__ __forceinline__ void rowq_eval(Lane &s, GridCtx &G, const RowPts &p) {
-  update4<MODE>(s, G, rcand<0>(s, p), rcand<1>(s, p), rcand<2>(s, p), rcand<3>(s, p));
-  update4<MODE>(s, G, rcand<4>(s, p), rcand<5>(s, p), rcand<6>(s, p), rcand<7>(s, p));
-  update4<MODE>(s, G, rcand<8>(s, p), rcand<9>(s, p), rcand<10>(s, p), rcand<11>(s, p));
-  update4<MODE>(s, G, rcand<12>(s, p), rcand<13>(s, p), rcand<14>(s, p), rcand<15>(s, p));
-  G.evals += 16u;
-#ifdef LSK_GRID_PROFILE
-  G.ev_mode[MODE] += 16u;
-#endif
-}
-
-// One level-lc cell: every row's segments are appended to its queue.
-__device__ __forceinline__ void cell_rows(GridCtx &G, const CellLoad &c, RowQ &Q) {
-  const bool ne = c.e > c.a;
-  const uint64_t nonempty = __ballot(ne);
-  if (!nonempty) return;
-  G.cells_n++;
-  const uint32_t sh = 10u - (G.lc + 2u);
-  const uint32_t last = (1023u >> sh);
-  float lx, hx, ly, hy, lz, hz;
-  cell_span(G, G.ox, c.xyz & 1023u, sh, last, lx, hx);
-  cell_span(G, G.oy, (c.xyz >> 10) & 1023u, sh, last, ly, hy);
-  cell_span(G, G.oz, c.xyz >> 20, sh, last, lz, hz);
-  uint64_t need[kCullGroups];
-#pragma unroll
-  for (int r = 0; r < kCullGroups; r++) {
-    const float *b = G.rbox + 8 * r;
-    const float g2 = lsk::dist2(gap1(lx, hx, b[0], b[3]), gap1(ly, hy, b[1], b[4]), gap1(lz, hz, b[2], b[5]));
-    need[r] = __ballot(ne && g2 <= b[6]);
-  }
-  uint32_t qa = Q.qa, qe = Q.qe, qn = Q.qn;
-#pragma unroll
-  for (int r = 0; r < kCullGroups; r++) {
-    uint64_t nd = need[r];
-    if (!nd) continue;
-    const uint64_t fr = nd | ~nonempty;  // runs of needed or empty slots are contiguous in memory
-    uint32_t t = lsk::uniform((uint32_t)__builtin_amdgcn_readlane((int)qn, 16 * r));
-    do {
-      const uint32_t t0 = (uint32_t)__builtin_ctzll(nd);
-      const uint64_t after = ~fr >> t0;
-      const uint32_t len = after ? (uint32_t)__builtin_ctzll(after) : 64u - t0;
-      const uint64_t run = (len >= 64u ? ~0ull : ((1ull << len) - 1ull)) << t0;
-      const uint32_t t1 = 63u - (uint32_t)__builtin_clzll(nd & run);
-      nd &= ~run;
-      const uint32_t a = lsk::uniform((uint32_t)__builtin_amdgcn_readlane((int)c.a, (int)t0));
-      const uint32_t e = lsk::uniform((uint32_t)__builtin_amdgcn_readlane((int)c.e, (int)t1));
-      // lane 16r + t takes the segment; past 16 entries lane 16r + 15 extends its end
-      const bool at = (uint32_t)G.lane == 16u * r + min(t, 15u);
-      qa = at && t < 16u ? a : qa;
-      qe = at ? e : qe;
-      t += t < 16u ? 1u : 0u;
-      G.segs++;
-    } while (nd);
-    qn = ((uint32_t)G.lane >> 4) == (uint32_t)r ? t : qn;
-  }
-  Q.qa = qa;
-  Q.qe = qe;
-  Q.qn = qn;
-}
-
-// One pass with per-row streams. The cells in range are visited in chunks of at most
-// 16 x 16 x (256 / 256..) cells (one chunk for a normal range), nearest first inside a
-// chunk: lane l holds chunk cells l, l+64, l+128, l+192 with their gap to the wave box.
-// A range of more than kMaxCells cells is one segment of all points per row (n <= kScanAll)
-// or the backstop (returns false).
-template <int MODE>
-__device__ __forceinline__ bool grid_pass_rows(Lane &s, GridCtx &G, uint32_t n) {
-  float r2 = cull_r2<MODE>(s, G);
-  if (fbits(r2) == 0u) return true;
-  const uint32_t sh = 10u - G.lc;
-  const float r = sqrtf(r2);
-  const uint32_t x0 = cell_of(G.wlx - r, G.ox, G.scale, sh), x1 = cell_of(G.whx + r, G.ox, G.scale, sh);
-  const uint32_t y0 = cell_of(G.wly - r, G.oy, G.scale, sh), y1 = cell_of(G.why + r, G.oy, G.scale, sh);
-  const uint32_t z0 = cell_of(G.wlz - r, G.oz, G.scale, sh), z1 = cell_of(G.whz + r, G.oz, G.scale, sh);
-  const uint32_t nx = x1 - x0 + 1u, ny = y1 - y0 + 1u, nz = z1 - z0 + 1u;
-  const bool scan_all = (uint64_t)nx * ny * nz > kMaxCells;
-  if (scan_all && n > kScanAll) return false;
-  const uint32_t cxn = min(nx, 16u), cyn = min(ny, 16u), czn = max(1u, min(nz, 256u / (cxn * cyn)));
-  const uint32_t ncx = (nx + cxn - 1u) / cxn, ncy = (ny + cyn - 1u) / cyn, ncz = (nz + czn - 1u) / czn;
-  const uint32_t nchunks = scan_all ? 0u : ncx * ncy * ncz;
-  uint32_t chunk = 0, bx = 0, by = 0, bz = 0, tx = 1, ty = 1, tot = 0, inx = 0, iny = 0;
-  const uint32_t l = (uint32_t)G.lane;
-  float g0 = __builtin_inff(), g1 = g0, g2 = g0, g3 = g0;
-  // chunk k: its origin and size (clipped at the range end) and the gaps of its cells
-  auto load_chunk = [&](uint32_t k) {
-    const uint32_t kx = k % ncx, ky = (k / ncx) % ncy, kz = k / (ncx * ncy);
-    bx = x0 + kx * cxn;
-    by = y0 + ky * cyn;
-    bz = z0 + kz * czn;
-    tx = min(cxn, x1 + 1u - bx);
-    ty = min(cyn, y1 + 1u - by);
-    const uint32_t tz = min(czn, z1 + 1u - bz);
-    tot = tx * ty * tz;
-    inx = (65536u + tx - 1u) / tx;  // exact for c < 256
-    iny = (65536u + ty - 1u) / ty;
-    auto gap_of = [&](uint32_t c) {
-      const uint32_t q = (c * inx) >> 16, rr = (q * iny) >> 16;
-      return c < tot ? cell_gap2(G, bx + c - q * tx, by + q - rr * ty, bz + rr, sh) : __builtin_inff();
-    };
-    g0 = gap_of(l);
-    g1 = tot > 64u ? gap_of(l + 64u) : __builtin_inff();
-    g2 = tot > 128u ? gap_of(l + 128u) : __builtin_inff();
-    g3 = tot > 192u ? gap_of(l + 192u) : __builtin_inff();
-  };
-  if (nchunks) load_chunk(0);
-  CellLoad pend{0u, 0u, 0u};
-  // the nearest cell still within the radius (next chunks when one is exhausted): its
-  // slots are fetched into pend
-  auto next_cell = [&]() -> bool {
-    for (;;) {
-      const float m = wave_min_nonneg(fminf(fminf(g0, g1), fminf(g2, g3)));
-      if (m <= r2) {
-        const uint64_t b0 = __ballot(g0 == m), b1 = __ballot(g1 == m), b2 = __ballot(g2 == m);
-        const uint32_t c = b0 ? (uint32_t)__builtin_ctzll(b0)
-                              : b1 ? 64u + (uint32_t)__builtin_ctzll(b1)
-                                   : b2 ? 128u + (uint32_t)__builtin_ctzll(b2)
-                                        : 192u + (uint32_t)__builtin_ctzll(__ballot(g3 == m));
-        if (l == (c & 63u)) {
-          const uint32_t slot = c >> 6;
-          g0 = slot == 0u ? __builtin_inff() : g0;
-          g1 = slot == 1u ? __builtin_inff() : g1;
-          g2 = slot == 2u ? __builtin_inff() : g2;
-          g3 = slot == 3u ? __builtin_inff() : g3;
-        }
-        const uint32_t q = (c * inx) >> 16, rr = (q * iny) >> 16;
-        pend = fetch_cell(G, bx + c - q * tx, by + q - rr * ty, bz + rr);
-        return true;
-      }
-      if (++chunk >= nchunks) return false;
-      load_chunk(chunk);
-    }
-  };
-  RowQ Q{0u, 0u, 0u};
-  bool have = false;
-  if (scan_all) {
-    // every row streams all points
-    Q.qe = (l & 15u) == 0u ? n : 0u;
-    Q.qn = 1u;
-  } else {
-    have = next_cell();
-    if (!have) return true;
-  }
-
-  // cells while a row runs low and no row's queue is full (the radius is re-read first)
-  auto refill = [&]() {
-    while (have && !__ballot(Q.qn >= 16u) && __ballot(Q.qn <= (uint32_t)LSK_ROWQ_LOW)) {
-      if (MODE == MODE_HIST) r2 = cull_r2<MODE>(s, G);
-#ifdef LSK_ROWQ_STATS
-      G.rq_refills++;
-#endif
-      cell_rows(G, pend, Q);
-      have = fbits(r2) != 0u && next_cell();
-    }
-    return __ballot(Q.qn > 0u) != 0ull;
-  };
-  if (!refill()) return true;
-  RowPts A = rowq_take(Q, G);
-  for (;;) {
-    bool more = refill();
-    RowPts B = rowq_take(Q, G);
-    rowq_eval<MODE>(s, G, A);
-    if (MODE == MODE_HIST) {
-      shrink_all<MODE>(s, G);
-      if (!__ballot(s.state == ST_HIST && s.hi_b > 0u)) break;
-    }
-    if (!more) break;
-    more = refill();
-    A = rowq_take(Q, G);
-    rowq_eval<MODE>(s, G, B);
-    if (MODE == MODE_HIST) {
-      shrink_all<MODE>(s, G);
-      if (!__ballot(s.state == ST_HIST && s.hi_b > 0u)) break;
-    }
-    if (!more) break;
-  }
-  return true;
-}
+#include "../../../scripts/micro/knn_grid_rowq.inc"
 #endif
 
 template <int MODE>
