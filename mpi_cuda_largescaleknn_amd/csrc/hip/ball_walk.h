@@ -1,5 +1,9 @@
-// The ball walk shared by the neighbour lists (knn_neighbors.hip) and the fixed-radius
-// search (radius.hip): one wave owns 64 curve-consecutive sorted queries (lane = query)
+// The ball walk shared by the neighbour lists (knn_neighbors.hip), the radius searches
+// (radius.hip, radius_var.hip), the clustering (cluster.hip), their periodic forms
+// (periodic.hip, knn_periodic.hip) and the profiles (radius_profile.hip), with the pieces
+// their exactness arguments rest on, each written once: the bucket scan, the span of a node,
+// the far-corner distance, the cover of an accepted node and the statistics.
+// One wave owns 64 curve-consecutive sorted queries (lane = query)
 // and walks the bucket tree once for the group. The DFS is wave-uniform with its stack in
 // LDS; an inner node is expanded to its descendants kWalkStep levels down, one box per
 // lane, and a bucket is scanned by the lanes whose own ball reaches it, its points
@@ -93,31 +97,158 @@ __device__ __forceinline__ box3f group_box(const GroupQuery &Q, bool live) {
           {wave_max(live ? Q.x : -inf), wave_max(live ? Q.y : -inf), wave_max(live ? Q.z : -inf)}};
 }
 
-// Scan bucket `node` (level T.depth): its points (and, kIds, their input rows perm[pos]) are
-// loaded one per lane and broadcast in order; a lane with `use` set calls cand(d2, id, use)
-// for each, and may clear `use` there to stop. Returns the bucket's point count.
-template <bool kIds, class Cand>
-__device__ __forceinline__ int scan_bucket(const lsk_tree_view &T, const uint32_t *perm, uint32_t node, int lane,
-                                           const GroupQuery &Q, bool &use, Cand cand) {
+// Sorted positions [p0, p1) of `node` at level lvl (its buckets, the last one clipped at n).
+__device__ __forceinline__ void node_span(const lsk_tree_view &T, uint32_t node, int32_t lvl, int64_t &p0,
+                                          int64_t &p1) {
+  const int32_t span_lg = T.depth - lvl;
+  const int64_t first = ((int64_t)node - ((int64_t)1 << lvl)) << span_lg;
+  p0 = first * kBucket;
+  p1 = min(T.n, (first + ((int64_t)1 << span_lg)) * kBucket);
+}
+
+// The canonical dist2 from (qx, qy, qz) to the farthest corner of a box. Per-axis float
+// differences, squares and fma are monotone, so no finite point inside the box has a larger
+// computed d² (knn_exact.hip::count_tree carries the same argument about its own centre).
+__device__ __forceinline__ float far_dist2(float qx, float qy, float qz, const float4 &lo4, const float4 &hi4) {
+  const float fx = fmaxf(fabsf(lo4.x - qx), fabsf(hi4.x - qx));
+  const float fy = fmaxf(fabsf(lo4.y - qy), fabsf(hi4.y - qy));
+  const float fz = fmaxf(fabsf(lo4.z - qz), fabsf(hi4.z - qz));
+  return dist2(fx, fy, fz);
+}
+
+// "This lane took a whole node when the stack stood at sp." The walk pops a node, then pushes
+// its descendants above the place it was popped from, so everything popped while the stack is
+// at least that high lies inside the taken node and the lane ignores it; the first pop below
+// ends the cover. on_node calls pop(sp) first, then asks on(); take(sp) starts a cover.
+struct Cover {
+  bool is = false;
+  uint32_t at = 0;
+  __device__ __forceinline__ void pop(uint32_t sp) {
+    if (is && sp < at) is = false;
+  }
+  __device__ __forceinline__ void take(uint32_t sp) {
+    is = true;
+    at = sp;
+  }
+  __device__ __forceinline__ bool on() const { return is; }
+  __device__ __forceinline__ void clear() { is = false; }  // a new walk (the next image)
+};
+
+// The per-point columns that travel with a bucket's points through scan_bucket: load(pi) reads
+// the lane's own point's value, get(j) broadcasts that of point j to the wave. NoCol is no
+// column at all: no register, no instruction.
+struct NoCol {
+  struct value {};
+  __device__ __forceinline__ void load(int64_t) {}
+  __device__ __forceinline__ value get(int) const { return {}; }
+};
+// An integer column of up to 32 bits, widened (the input rows perm[pos], the core flags).
+// !kOn: the column of a kernel form that has the value in its code but never reads it (the
+// ids of a count walk): the constant 0, as free as NoCol.
+template <class T, bool kOn = true>
+struct Col {
+  static_assert(sizeof(T) <= 4, "one readlane per value");
+  const T *p;
+  uint32_t r = 0;
+  __device__ __forceinline__ void load(int64_t pi) {
+    if (kOn) r = (uint32_t)p[pi];
+  }
+  __device__ __forceinline__ uint32_t get(int j) const {
+    return kOn ? (uint32_t)__builtin_amdgcn_readlane((int)r, j) : 0u;
+  }
+};
+struct FloatCol {  // (the per-point cutoffs)
+  const float *p;
+  float r = 0.f;
+  __device__ __forceinline__ void load(int64_t pi) { r = p[pi]; }
+  __device__ __forceinline__ float get(int j) const { return readlane_f(r, j); }
+};
+struct WeightCol {  // int64 weights as wrapping unsigned: two readlanes
+  const int64_t *p;
+  uint32_t lo = 0, hi = 0;
+  __device__ __forceinline__ void load(int64_t pi) {
+    const unsigned long long w = (unsigned long long)p[pi];
+    lo = (uint32_t)w;
+    hi = (uint32_t)(w >> 32);
+  }
+  __device__ __forceinline__ unsigned long long get(int j) const {
+    const uint32_t l = (uint32_t)__builtin_amdgcn_readlane((int)lo, j);
+    const uint32_t h = (uint32_t)__builtin_amdgcn_readlane((int)hi, j);
+    return ((unsigned long long)h << 32) | (unsigned long long)l;
+  }
+};
+
+// The open-box difference of scan_bucket: the canonical d² of Q - p; every candidate is `mine`.
+// (periodic_image.h has the periodic one.)
+struct OpenDiff {
+  __device__ __forceinline__ float operator()(const GroupQuery &Q, float x, float y, float z, bool &mine) const {
+    mine = true;
+    return dist2(Q.x - x, Q.y - y, Q.z - z);
+  }
+};
+
+// What scan_bucket hands to its functor per candidate: d² under the scan's difference, whether
+// the pair belongs to the walk's image (open box: always), the candidate's sorted position and
+// the values of the two columns.
+template <class A, class B>
+struct Candidate {
+  float d2;
+  bool mine;
+  uint32_t pos;
+  A a;
+  B b;
+};
+
+// Scan bucket `node` (level T.depth): its points, and the columns `ca` / `cb` beside them, are
+// loaded one per lane and broadcast in order; a lane with `use` set calls cand(c, use) with
+// the Candidate c of each, and may clear `use` there to stop. Returns the bucket's point
+// count. The only load-and-broadcast loop of the walks: what differs between them is `diff`
+// and the columns.
+template <class Diff, class ColA, class ColB, class Cand>
+__device__ __forceinline__ int scan_bucket(const lsk_tree_view &T, uint32_t node, int lane, const GroupQuery &Q,
+                                           const Diff &diff, ColA ca, ColB cb, bool &use, Cand cand) {
   const int64_t base = ((int64_t)node - ((int64_t)1 << T.depth)) * kBucket;
   if (base >= T.n) return 0;
   const int cnt = (int)min((int64_t)kBucket, T.n - base);
   const int64_t pi = base + lane;
   float px = 0.f, py = 0.f, pz = 0.f;
-  uint32_t pid = 0;
   if (lane < cnt) {
     px = T.pts[3 * pi];
     py = T.pts[3 * pi + 1];
     pz = T.pts[3 * pi + 2];
-    if (kIds) pid = perm[pi];
+    ca.load(pi);
+    cb.load(pi);
   }
   for (int j = 0; j < cnt; j++) {
     const float x = readlane_f(px, j), y = readlane_f(py, j), z = readlane_f(pz, j);
-    uint32_t id = 0;
-    if (kIds) id = (uint32_t)__builtin_amdgcn_readlane((int)pid, j);
-    if (use) cand(dist2(Q.x - x, Q.y - y, Q.z - z), id, use);
+    auto a = ca.get(j);
+    auto b = cb.get(j);
+    if (use) {
+      bool mine;
+      const float d2 = diff(Q, x, y, z, mine);
+      cand(Candidate<decltype(a), decltype(b)>{d2, mine, (uint32_t)(base + j), a, b}, use);
+    }
   }
   return cnt;
+}
+
+// The statistics of a walk, added to stats[0 .. 3] (and, kFifth, stats[4]) by one lane per
+// wave: distance evaluations and whole-box acceptances are per lane and summed here, as is
+// `fifth` (the CAS retries of the clustering hooks; a wave-uniform count, the image walks of
+// the periodic kernels, comes from lane 0 alone); nodes popped and buckets scanned are
+// wave-uniform. stats may be null.
+template <bool kFifth>
+__device__ __forceinline__ void add_stats(unsigned long long *stats, int lane, uint32_t evals, uint32_t nodes,
+                                          uint32_t buckets, uint32_t accepts, uint32_t fifth = 0u) {
+  if (!stats) return;
+  const uint32_t e = wave_sum(evals), a = wave_sum(accepts), f = kFifth ? wave_sum(fifth) : 0u;
+  if (lane == 0) {
+    atomicAdd(&stats[0], (unsigned long long)e);
+    atomicAdd(&stats[1], (unsigned long long)nodes);
+    atomicAdd(&stats[2], (unsigned long long)buckets);
+    atomicAdd(&stats[3], (unsigned long long)a);
+    if (kFifth) atomicAdd(&stats[4], (unsigned long long)f);
+  }
 }
 
 // The DFS. Every popped bucket, and with kTestInner every popped inner node too, has its own

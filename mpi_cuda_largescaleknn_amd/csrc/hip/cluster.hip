@@ -27,7 +27,7 @@
 //     finite and core. Per candidate with d² < cut2 that is core: unite(pos_q, pos_p). Inside
 //     a clique node a lane needs one hit only: if the node's far corner is < cut2 it unites
 //     with the node's first position without a distance evaluation, otherwise it descends
-//     and leaves the subtree after its first hit (cov / cov_sp as in the count walk). A wave
+//     and leaves the subtree after its first hit (CliqueCover of cluster_uf.h). A wave
 //     whose own bucket is a clique skips every bucket that is none: a core point x of such a
 //     bucket is live in its own wave, whose walk reaches this wave's clique (some point of it
 //     is within cut2 of x) and takes a hit there, and all of the clique is linked already.
@@ -61,7 +61,6 @@
 
 namespace {
 
-using lsk::add_stats;
 using lsk::all_core;
 using lsk::fbits;
 using lsk::load_own;
@@ -120,35 +119,6 @@ __global__ __launch_bounds__(kWaves * 64) void cluster_init_kernel(const Cluster
   }
 }
 
-// scan_bucket of ball_walk.h with the candidates' core flags travelling beside them:
-// cand(d2, core flag, sorted position, input row (kIds), use).
-template <bool kIds, class Cand>
-__device__ __forceinline__ int scan_bucket_core(const lsk_tree_view &T, const uint32_t *perm, const uint8_t *core,
-                                                uint32_t node, int lane, const lsk::GroupQuery &Q, bool &use,
-                                                Cand cand) {
-  const int64_t base = ((int64_t)node - ((int64_t)1 << T.depth)) * lsk::kBucket;
-  if (base >= T.n) return 0;
-  const int cnt = (int)min((int64_t)lsk::kBucket, T.n - base);
-  const int64_t pi = base + lane;
-  float px = 0.f, py = 0.f, pz = 0.f;
-  uint32_t pid = 0, pc = 0;
-  if (lane < cnt) {
-    px = T.pts[3 * pi];
-    py = T.pts[3 * pi + 1];
-    pz = T.pts[3 * pi + 2];
-    pc = core[pi];
-    if (kIds) pid = perm[pi];
-  }
-  for (int j = 0; j < cnt; j++) {
-    const float x = lsk::readlane_f(px, j), y = lsk::readlane_f(py, j), z = lsk::readlane_f(pz, j);
-    const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)pc, j);
-    uint32_t id = 0;
-    if (kIds) id = (uint32_t)__builtin_amdgcn_readlane((int)pid, j);
-    if (use) cand(lsk::dist2(Q.x - x, Q.y - y, Q.z - z), c, (uint32_t)(base + j), id, use);
-  }
-  return cnt;
-}
-
 __global__ __launch_bounds__(kWaves * 64) void cluster_hook_kernel(const ClusterArgs A) {
   __shared__ uint32_t stk_all[kWaves][lsk::kWalkStack];
   const int wid = threadIdx.x >> 6;
@@ -165,10 +135,7 @@ __global__ __launch_bounds__(kWaves * 64) void cluster_hook_kernel(const Cluster
   if (!__ballot(live)) return;
   uint32_t rq = pos_q;  // a position of the lane's component, as low as the lane has seen
   bool bad = false;
-  // the lane is done with a whole node since the stack stood at cov_sp (count walk of
-  // radius.hip); inside a clique node entered at one_sp it is after one hit only
-  bool cov = false, one = false;
-  uint32_t cov_sp = 0, one_sp = 0;
+  lsk::CliqueCover cc;  // the node the lane is done with; the clique it wants one hit from
   uint32_t s_evals = 0, s_accepts = 0, s_nodes = 0, s_buckets = 0, s_retries = 0;
   const bool half = A.half != 0;
 
@@ -183,20 +150,14 @@ __global__ __launch_bounds__(kWaves * 64) void cluster_hook_kernel(const Cluster
     node_span(T, leaf, T.depth, p0, p1);
     own_clique = tight(nodes[2 * leaf], nodes[2 * leaf + 1], cut2) && all_core(A.cpre, p0, p1);
   }
-  // one hit inside the clique the lane is in: the rest of that clique's subtree is covered
-  auto hit = [&](uint32_t sp) {
-    cov = true;
-    cov_sp = one ? one_sp : sp;
-    one = false;
-  };
   lsk::ball_walk<true>(
       T, stk_all[wid], lane,
       [&](const float4 &lo4, const float4 &hi4) { return lsk::box_box_dist2(gb, lsk::box_of(lo4, hi4)) < cut2; },
       [&](uint32_t node, int32_t lvl, uint32_t sp, const float4 &lo4, const float4 &hi4) {
         s_nodes++;
-        if (cov && sp < cov_sp) cov = false;
-        if (one && sp < one_sp) one = false;
-        bool use = live && !bad && !cov && lsk::box_dist2(q, {lo4.x, lo4.y, lo4.z}, {hi4.x, hi4.y, hi4.z}) < cut2;
+        cc.pop(sp);
+        bool use =
+            live && !bad && !cc.cov.on() && lsk::box_dist2(q, {lo4.x, lo4.y, lo4.z}, {hi4.x, hi4.y, hi4.z}) < cut2;
         bool clique = false;  // (wave-uniform)
         int64_t p0 = 0, p1 = 0;
         if (__ballot(use) && tight(lo4, hi4, cut2)) {
@@ -209,17 +170,13 @@ __global__ __launch_bounds__(kWaves * 64) void cluster_hook_kernel(const Cluster
           if (own_clique && lvl == T.depth) use = false;
         } else {
           if (use) {  // a clique node: one hit will do
-            const float fx = fmaxf(fabsf(lo4.x - qx), fabsf(hi4.x - qx));
-            const float fy = fmaxf(fabsf(lo4.y - qy), fabsf(hi4.y - qy));
-            const float fz = fmaxf(fabsf(lo4.z - qz), fabsf(hi4.z - qz));
-            if (lsk::dist2(fx, fy, fz) < cut2) {  // every point of it is linked to the lane's
+            if (lsk::far_dist2(qx, qy, qz, lo4, hi4) < cut2) {  // every point of it is linked to the lane's
               unite(A.parent, rq, (uint32_t)p0, n, bad, s_retries);
-              hit(sp);
+              cc.hit(sp);
               use = false;
               s_accepts++;
-            } else if (!one) {
-              one = true;
-              one_sp = sp;
+            } else {
+              cc.enter(sp);
             }
           }
         }
@@ -227,12 +184,14 @@ __global__ __launch_bounds__(kWaves * 64) void cluster_hook_kernel(const Cluster
       },
       [&](uint32_t node, bool use) {
         const bool evals = use;
-        const int cnt = scan_bucket_core<false>(
-            T, A.perm, A.core, node, lane, Q, use, [&](float d2, uint32_t c, uint32_t pos, uint32_t, bool &use) {
-              if (d2 < cut2 && c) {
-                if (pos != pos_q && (one || !half || pos < pos_q)) unite(A.parent, rq, pos, n, bad, s_retries);
+        const int cnt = lsk::scan_bucket(
+            T, node, lane, Q, lsk::OpenDiff{}, lsk::Col<uint8_t>{A.core}, lsk::NoCol{}, use,
+            [&](const auto &c, bool &use) {  // (c.a: the candidate's core flag)
+              if (c.d2 < cut2 && c.a) {
+                const bool one = cc.one.on();
+                if (c.pos != pos_q && (one || !half || c.pos < pos_q)) unite(A.parent, rq, c.pos, n, bad, s_retries);
                 if (one) {
-                  hit(0);
+                  cc.hit(0);
                   use = false;
                 }
                 if (bad) use = false;
@@ -242,7 +201,7 @@ __global__ __launch_bounds__(kWaves * 64) void cluster_hook_kernel(const Cluster
         if (evals) s_evals += (uint32_t)cnt;
       });
   if (bad) atomicAdd(A.err, 1u);
-  add_stats(A.stats, lane, s_evals, s_nodes, s_buckets, s_accepts, s_retries);
+  lsk::add_stats<true>(A.stats, lane, s_evals, s_nodes, s_buckets, s_accepts, s_retries);
 }
 
 __global__ __launch_bounds__(256) void cluster_flatten_kernel(const ClusterArgs A) {
@@ -323,21 +282,21 @@ __global__ __launch_bounds__(kWaves * 64) void cluster_border_kernel(const Clust
       },
       [&](uint32_t node, bool use) {
         const bool evals = use;
-        const int cnt = scan_bucket_core<true>(T, A.perm, A.core, node, lane, Q, use,
-                                               [&](float d2, uint32_t c, uint32_t pos, uint32_t id, bool &) {
-                                                 if (d2 < cut2 && c) {
-                                                   const uint64_t key = ((uint64_t)fbits(d2) << 32) | id;
-                                                   if (key < best) {
-                                                     best = key;
-                                                     best_pos = pos;
-                                                   }
-                                                 }
-                                               });
+        const int cnt = lsk::scan_bucket(T, node, lane, Q, lsk::OpenDiff{}, lsk::Col<uint32_t>{A.perm},
+                                         lsk::Col<uint8_t>{A.core}, use, [&](const auto &c, bool &) {
+                                           if (c.d2 < cut2 && c.b) {  // (c.a: input row, c.b: core flag)
+                                             const uint64_t key = ((uint64_t)fbits(c.d2) << 32) | c.a;
+                                             if (key < best) {
+                                               best = key;
+                                               best_pos = c.pos;
+                                             }
+                                           }
+                                         });
         if (cnt) s_buckets++;
         if (evals) s_evals += (uint32_t)cnt;
       });
   if (live && best != ~0ull) A.labels[A.perm[Q.qi]] = (int32_t)A.minrow[A.root[best_pos]];
-  add_stats(A.stats, lane, s_evals, s_nodes, s_buckets, 0u, 0u);
+  lsk::add_stats<true>(A.stats, lane, s_evals, s_nodes, s_buckets, 0u, 0u);
 }
 
 int cluster_args(const char *what, const lsk_tree_view *tree, const uint8_t *core, float cut2, ClusterArgs *A) {

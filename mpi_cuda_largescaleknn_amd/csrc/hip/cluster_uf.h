@@ -6,14 +6,28 @@
 
 namespace lsk {
 
-// Sorted positions [p0, p1) of `node` at level lvl (its buckets, the last one clipped at n).
-__device__ __forceinline__ void node_span(const lsk_tree_view &T, uint32_t node, int32_t lvl, int64_t &p0,
-                                          int64_t &p1) {
-  const int32_t span_lg = T.depth - lvl;
-  const int64_t first = ((int64_t)node - ((int64_t)1 << lvl)) << span_lg;
-  p0 = first * kBucket;
-  p1 = min(T.n, (first + ((int64_t)1 << span_lg)) * kBucket);
-}
+// The Cover of a hook walk. Besides the node a lane is done with (`cov`), the clique node it is
+// inside and needs one hit from (`one`): entered where its far corner was not below the
+// cutoff, so the lane descends, and its first hit covers the rest of that clique's subtree.
+struct CliqueCover {
+  Cover cov, one;
+  __device__ __forceinline__ void pop(uint32_t sp) {
+    cov.pop(sp);
+    one.pop(sp);
+  }
+  __device__ __forceinline__ void enter(uint32_t sp) {
+    if (!one.on()) one.take(sp);
+  }
+  // a hit at sp: inside a clique entered before, all of that clique is covered
+  __device__ __forceinline__ void hit(uint32_t sp) {
+    cov.take(one.on() ? one.at : sp);
+    one.clear();
+  }
+  __device__ __forceinline__ void clear() {
+    cov.clear();
+    one.clear();
+  }
+};
 
 __device__ __forceinline__ bool tight(const float4 &lo4, const float4 &hi4, float cut2) {
   return dist2(hi4.x - lo4.x, hi4.y - lo4.y, hi4.z - lo4.z) < cut2;
@@ -79,19 +93,6 @@ __device__ __forceinline__ GroupQuery load_own(const lsk_tree_view &T, int64_t g
   }
   Q.finite = Q.valid && finite3(Q.x, Q.y, Q.z);
   return Q;
-}
-
-__device__ __forceinline__ void add_stats(unsigned long long *stats, int lane, uint32_t evals, uint32_t nodes,
-                                          uint32_t buckets, uint32_t accepts, uint32_t retries) {
-  if (!stats) return;
-  const uint32_t e = wave_sum(evals), a = wave_sum(accepts), r = wave_sum(retries);
-  if (lane == 0) {
-    atomicAdd(&stats[0], (unsigned long long)e);
-    atomicAdd(&stats[1], (unsigned long long)nodes);
-    atomicAdd(&stats[2], (unsigned long long)buckets);
-    atomicAdd(&stats[3], (unsigned long long)a);
-    atomicAdd(&stats[4], (unsigned long long)r);
-  }
 }
 
 }  // namespace lsk

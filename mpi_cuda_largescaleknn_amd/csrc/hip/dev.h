@@ -54,6 +54,12 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
 }
+// (64-bit, wrapping; equal in every lane, not made uniform: its users store it from one lane)
+__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
 
 // K-th smallest (1-based) of a per-lane uint32 over the wave, by a bitwise ballot
 // search (32 rounds of compare + ballot + popcount); uniform result.

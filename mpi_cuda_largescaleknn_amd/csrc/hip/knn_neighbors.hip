@@ -82,7 +82,10 @@ __global__ __launch_bounds__(kWaves * 64) void nb_collect_kernel(const NbArgs A)
           return live && !bad && lsk::box_dist2(q, {lo4.x, lo4.y, lo4.z}, {hi4.x, hi4.y, hi4.z}) <= r;
         },
         [&](uint32_t node, bool use) {
-          lsk::scan_bucket<true>(A.T, A.perm, node, lane, Q, use, [&](float d2, uint32_t id, bool &use) {
+          lsk::scan_bucket(A.T, node, lane, Q, lsk::OpenDiff{}, lsk::Col<uint32_t>{A.perm}, lsk::NoCol{}, use,
+                           [&](const auto &c, bool &use) {
+            const float d2 = c.d2;
+            const uint32_t id = c.a;
             if (d2 < r) {
               if (front + 1u >= k) {  // more than k - 1 values below the k-th: stop appending
                 bad = true;

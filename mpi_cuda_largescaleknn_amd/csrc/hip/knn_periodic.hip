@@ -142,15 +142,15 @@ __global__ __launch_bounds__(kWaves * 64) void pknn_walk_kernel(const PknnWalkAr
           },
           [&](uint32_t node, bool use) {
             const bool evals = use;
-            const int cnt = scan_bucket_periodic<kFill, false>(
-                T, A.perm, nullptr, node, lane, Q, F, I, use,
-                [&](float d2, bool mine, uint32_t, uint32_t, uint32_t id, bool &use) {
-                  if (mine && d2 < cut2) {
+            const int cnt = lsk::scan_bucket(
+                T, node, lane, Q, ImageDiff{F, I}, lsk::Col<uint32_t, kFill>{A.perm}, lsk::NoCol{}, use,
+                [&](const auto &c, bool &use) {
+                  if (c.mine && c.d2 < cut2) {
                     if (!kFill) {
                       count++;
                     } else if (cur < end) {
-                      A.out_idx[cur] = (int32_t)id;
-                      A.out_dist[cur] = fbits(d2);
+                      A.out_idx[cur] = (int32_t)c.a;
+                      A.out_dist[cur] = fbits(c.d2);
                       cur++;
                     } else {  // more than the count pass saw: stop appending
                       bad = true;
@@ -166,15 +166,7 @@ __global__ __launch_bounds__(kWaves * 64) void pknn_walk_kernel(const PknnWalkAr
 
   if (!kFill) {
     if (Q.valid) A.counts[row] = (int32_t)count;
-    if (A.stats) {
-      const uint32_t e = lsk::wave_sum(s_evals);
-      if (lane == 0) {
-        atomicAdd(&A.stats[0], (unsigned long long)e);
-        atomicAdd(&A.stats[1], (unsigned long long)s_nodes);
-        atomicAdd(&A.stats[2], (unsigned long long)s_buckets);
-        atomicAdd(&A.stats[4], (unsigned long long)s_images);
-      }
-    }
+    lsk::add_stats<true>(A.stats, lane, s_evals, s_nodes, s_buckets, 0u, lane == 0 ? s_images : 0u);
   } else if (Q.valid && (bad || cur != end)) {
     atomicAdd(A.err, 1u);
   }

@@ -48,6 +48,7 @@
 // cut2) has extent a per axis with fl(a a) <= dist2(diagonal) < cut2 <= fl(h h), and fl(a a)
 // < fl(h h) implies a < h: no pair inside wraps, pd2 is the open-box d², and the clique
 // pre-linking of cluster_init_kernel holds unchanged.
+#include "cluster_uf.h"
 #include "periodic_image.h"
 
 namespace {
@@ -99,9 +100,7 @@ __global__ __launch_bounds__(kWaves * 64) void radius_periodic_walk_kernel(const
   const bool live = Q.finite && cut2 > 0.f;
   uint32_t count = 0;
   bool bad = false;
-  // count: as radius.hip, the lane took a whole node when the stack stood at cov_sp
-  bool cov = false;
-  uint32_t cov_sp = 0;
+  lsk::Cover cov;  // count: the whole node the lane took
   uint32_t s_evals = 0, s_accepts = 0, s_nodes = 0, s_buckets = 0, s_images = 0;
 
   if (__ballot(live)) {
@@ -114,7 +113,7 @@ __global__ __launch_bounds__(kWaves * 64) void radius_periodic_walk_kernel(const
       if (!image_of(F.X, F.Y, F.Z, im, I)) continue;
       if (!(image_box_dist2(gb, F.rlo, F.rhi, I) < gmax)) continue;
       s_images++;
-      cov = false;
+      cov.clear();
       lsk::ball_walk<true>(
           T, stk_all[wid], lane,
           [&](const float4 &lo4, const float4 &hi4) { return image_box_dist2(gb, lo4, hi4, I) < gmax; },
@@ -122,15 +121,14 @@ __global__ __launch_bounds__(kWaves * 64) void radius_periodic_walk_kernel(const
             s_nodes++;
             bool use = live && !bad && image_point_dist2(Q, lo4, hi4, I) < cut2;
             if (!kFill) {
-              if (cov && sp < cov_sp) cov = false;
-              use = use && !cov;
+              cov.pop(sp);
+              use = use && !cov.on();
               if (use && box_inside(Q, lo4, hi4, F.X, F.Y, F.Z, I, cut2)) {
                 // the node's points: its buckets, the last one clipped at n
                 int64_t p0, p1;
                 lsk::node_span(T, node, lvl, p0, p1);
                 if (p1 > p0) count += (uint32_t)(p1 - p0);
-                cov = true;
-                cov_sp = sp;
+                cov.take(sp);
                 use = false;
                 s_accepts++;
               }
@@ -139,15 +137,15 @@ __global__ __launch_bounds__(kWaves * 64) void radius_periodic_walk_kernel(const
           },
           [&](uint32_t node, bool use) {
             const bool evals = use;
-            const int cnt = scan_bucket_periodic<kFill, false>(
-                T, A.perm, nullptr, node, lane, Q, F, I, use,
-                [&](float d2, bool mine, uint32_t, uint32_t, uint32_t id, bool &use) {
-                  if (mine && d2 < cut2) {
+            const int cnt = lsk::scan_bucket(
+                T, node, lane, Q, ImageDiff{F, I}, lsk::Col<uint32_t, kFill>{A.perm}, lsk::NoCol{}, use,
+                [&](const auto &c, bool &use) {
+                  if (c.mine && c.d2 < cut2) {
                     if (!kFill) {
                       count++;
                     } else if (cur < end) {
-                      A.out_idx[cur] = (int32_t)id;
-                      A.out_dist[cur] = fbits(d2);
+                      A.out_idx[cur] = (int32_t)c.a;
+                      A.out_dist[cur] = fbits(c.d2);
                       cur++;
                     } else {  // more than the count pass saw: stop appending
                       bad = true;
@@ -163,16 +161,7 @@ __global__ __launch_bounds__(kWaves * 64) void radius_periodic_walk_kernel(const
 
   if (!kFill) {
     if (Q.valid) A.counts[row] = (int32_t)count;
-    if (A.stats) {
-      const uint32_t e = lsk::wave_sum(s_evals), a = lsk::wave_sum(s_accepts);
-      if (lane == 0) {
-        atomicAdd(&A.stats[0], (unsigned long long)e);
-        atomicAdd(&A.stats[1], (unsigned long long)s_nodes);
-        atomicAdd(&A.stats[2], (unsigned long long)s_buckets);
-        atomicAdd(&A.stats[3], (unsigned long long)a);
-        atomicAdd(&A.stats[4], (unsigned long long)s_images);
-      }
-    }
+    lsk::add_stats<true>(A.stats, lane, s_evals, s_nodes, s_buckets, s_accepts, lane == 0 ? s_images : 0u);
   } else if (Q.valid && (bad || cur != end)) {
     atomicAdd(A.err, 1u);
   }
@@ -217,8 +206,7 @@ __global__ __launch_bounds__(kWaves * 64) void cluster_periodic_hook_kernel(cons
   if (!__ballot(live)) return;
   uint32_t rq = pos_q;  // a position of the lane's component, as low as the lane has seen
   bool bad = false;
-  bool cov = false, one = false;
-  uint32_t cov_sp = 0, one_sp = 0;
+  lsk::CliqueCover cc;
   uint32_t s_evals = 0, s_accepts = 0, s_nodes = 0, s_buckets = 0, s_retries = 0;
   const bool half = A.half != 0;
 
@@ -233,26 +221,18 @@ __global__ __launch_bounds__(kWaves * 64) void cluster_periodic_hook_kernel(cons
     lsk::node_span(T, leaf, T.depth, p0, p1);
     own_clique = lsk::tight(nodes[2 * leaf], nodes[2 * leaf + 1], cut2) && lsk::all_core(A.cpre, p0, p1);
   }
-  // one hit inside the clique the lane is in: the rest of that clique's subtree is covered
-  auto hit = [&](uint32_t sp) {
-    cov = true;
-    cov_sp = one ? one_sp : sp;
-    one = false;
-  };
   for (int im = 0; im < 27; im++) {  // (wave-uniform)
     Image I;
     if (!image_of(F.X, F.Y, F.Z, im, I)) continue;
     if (!(image_box_dist2(gb, F.rlo, F.rhi, I) < cut2)) continue;
-    cov = false;
-    one = false;
+    cc.clear();
     lsk::ball_walk<true>(
         T, stk_all[wid], lane,
         [&](const float4 &lo4, const float4 &hi4) { return image_box_dist2(gb, lo4, hi4, I) < cut2; },
         [&](uint32_t node, int32_t lvl, uint32_t sp, const float4 &lo4, const float4 &hi4) {
           s_nodes++;
-          if (cov && sp < cov_sp) cov = false;
-          if (one && sp < one_sp) one = false;
-          bool use = live && !bad && !cov && image_point_dist2(Q, lo4, hi4, I) < cut2;
+          cc.pop(sp);
+          bool use = live && !bad && !cc.cov.on() && image_point_dist2(Q, lo4, hi4, I) < cut2;
           bool clique = false;  // (wave-uniform)
           int64_t p0 = 0, p1 = 0;
           if (__ballot(use) && lsk::tight(lo4, hi4, cut2)) {
@@ -264,25 +244,26 @@ __global__ __launch_bounds__(kWaves * 64) void cluster_periodic_hook_kernel(cons
           } else if (use) {  // a clique node: one hit will do
             if (box_inside(Q, lo4, hi4, F.X, F.Y, F.Z, I, cut2)) {  // every point of it is linked to the lane's
               lsk::unite(A.parent, rq, (uint32_t)p0, n, bad, s_retries);
-              hit(sp);
+              cc.hit(sp);
               use = false;
               s_accepts++;
-            } else if (!one) {
-              one = true;
-              one_sp = sp;
+            } else {
+              cc.enter(sp);
             }
           }
           return use;
         },
         [&](uint32_t node, bool use) {
           const bool evals = use;
-          const int cnt = scan_bucket_periodic<false, true>(
-              T, nullptr, A.core, node, lane, Q, F, I, use,
-              [&](float d2, bool mine, uint32_t c, uint32_t pos, uint32_t, bool &use) {
-                if (mine && d2 < cut2 && c) {
-                  if (pos != pos_q && (one || !half || pos < pos_q)) lsk::unite(A.parent, rq, pos, n, bad, s_retries);
+          const int cnt = lsk::scan_bucket(
+              T, node, lane, Q, ImageDiff{F, I}, lsk::Col<uint8_t>{A.core}, lsk::NoCol{}, use,
+              [&](const auto &c, bool &use) {  // (c.a: the candidate's core flag)
+                if (c.mine && c.d2 < cut2 && c.a) {
+                  const bool one = cc.one.on();
+                  if (c.pos != pos_q && (one || !half || c.pos < pos_q))
+                    lsk::unite(A.parent, rq, c.pos, n, bad, s_retries);
                   if (one) {
-                    hit(0);
+                    cc.hit(0);
                     use = false;
                   }
                   if (bad) use = false;
@@ -293,7 +274,7 @@ __global__ __launch_bounds__(kWaves * 64) void cluster_periodic_hook_kernel(cons
         });
   }
   if (bad) atomicAdd(A.err, 1u);
-  lsk::add_stats(A.stats, lane, s_evals, s_nodes, s_buckets, s_accepts, s_retries);
+  lsk::add_stats<true>(A.stats, lane, s_evals, s_nodes, s_buckets, s_accepts, s_retries);
 }
 
 // The border walk of cluster.hip: the best (pd2 bits << 32 | input row) over all images.
@@ -329,14 +310,14 @@ __global__ __launch_bounds__(kWaves * 64) void cluster_periodic_border_kernel(co
         },
         [&](uint32_t node, bool use) {
           const bool evals = use;
-          const int cnt = scan_bucket_periodic<true, true>(
-              T, A.perm, A.core, node, lane, Q, F, I, use,
-              [&](float d2, bool mine, uint32_t c, uint32_t pos, uint32_t id, bool &) {
-                if (mine && d2 < cut2 && c) {
-                  const uint64_t key = ((uint64_t)fbits(d2) << 32) | id;
+          const int cnt = lsk::scan_bucket(
+              T, node, lane, Q, ImageDiff{F, I}, lsk::Col<uint32_t>{A.perm}, lsk::Col<uint8_t>{A.core}, use,
+              [&](const auto &c, bool &) {
+                if (c.mine && c.d2 < cut2 && c.b) {  // (c.a: input row, c.b: core flag)
+                  const uint64_t key = ((uint64_t)fbits(c.d2) << 32) | c.a;
                   if (key < best) {
                     best = key;
-                    best_pos = pos;
+                    best_pos = c.pos;
                   }
                 }
               });
@@ -345,7 +326,7 @@ __global__ __launch_bounds__(kWaves * 64) void cluster_periodic_border_kernel(co
         });
   }
   if (live && best != ~0ull) A.labels[A.perm[Q.qi]] = (int32_t)A.minrow[A.root[best_pos]];
-  lsk::add_stats(A.stats, lane, s_evals, s_nodes, s_buckets, 0u, 0u);
+  lsk::add_stats<true>(A.stats, lane, s_evals, s_nodes, s_buckets, 0u, 0u);
 }
 
 // period: three values > 0 (+inf: open); bound: the largest squared cutoff, which must not

@@ -1,9 +1,9 @@
 // The image helpers of the periodic walks (periodic.hip, knn_periodic.hip): a group's axes
 // against the root box, the images it can take, the slackened gaps of the conservative cull,
-// the whole-box acceptance and the bucket scan with the minimum image of the difference.
+// the whole-box acceptance and the minimum image of the difference for the bucket scan.
 // periodic.hip states the contract and proves each step.
 #pragma once
-#include "cluster_uf.h"
+#include "ball_walk.h"
 
 namespace lsk {
 namespace periodic {
@@ -131,40 +131,20 @@ __device__ __forceinline__ Frame make_frame(const lsk_tree_view &T, const float 
   return F;
 }
 
-// scan_bucket of ball_walk.h under the period: cand(pd2, the pair's wrap vector is the
-// image's, core flag (kCore), sorted position, input row (kIds), use).
-template <bool kIds, bool kCore, class Cand>
-__device__ __forceinline__ int scan_bucket_periodic(const lsk_tree_view &T, const uint32_t *perm,
-                                                    const uint8_t *core, uint32_t node, int lane,
-                                                    const lsk::GroupQuery &Q, const Frame &F, const Image &I,
-                                                    bool &use, Cand cand) {
-  const int64_t base = ((int64_t)node - ((int64_t)1 << T.depth)) * lsk::kBucket;
-  if (base >= T.n) return 0;
-  const int cnt = (int)min((int64_t)lsk::kBucket, T.n - base);
-  const int64_t pi = base + lane;
-  float px = 0.f, py = 0.f, pz = 0.f;
-  uint32_t pid = 0, pc = 0;
-  if (lane < cnt) {
-    px = T.pts[3 * pi];
-    py = T.pts[3 * pi + 1];
-    pz = T.pts[3 * pi + 2];
-    if (kCore) pc = core[pi];
-    if (kIds) pid = perm[pi];
+// The difference of scan_bucket (ball_walk.h) under the period: pd2 of the minimum image, and
+// `mine` = the pair's wrap vector is the image's.
+struct ImageDiff {
+  const Frame &F;
+  const Image &I;
+  __device__ __forceinline__ float operator()(const lsk::GroupQuery &Q, float x, float y, float z,
+                                              bool &mine) const {
+    int wx, wy, wz;
+    const float dx = wrap1(Q.x - x, F.X.L, F.X.h, wx), dy = wrap1(Q.y - y, F.Y.L, F.Y.h, wy),
+                dz = wrap1(Q.z - z, F.Z.L, F.Z.h, wz);
+    mine = wx == I.x.s && wy == I.y.s && wz == I.z.s;
+    return lsk::dist2(dx, dy, dz);
   }
-  for (int j = 0; j < cnt; j++) {
-    const float x = lsk::readlane_f(px, j), y = lsk::readlane_f(py, j), z = lsk::readlane_f(pz, j);
-    uint32_t c = 1, id = 0;
-    if (kCore) c = (uint32_t)__builtin_amdgcn_readlane((int)pc, j);
-    if (kIds) id = (uint32_t)__builtin_amdgcn_readlane((int)pid, j);
-    if (use) {
-      int wx, wy, wz;
-      const float dx = wrap1(Q.x - x, F.X.L, F.X.h, wx), dy = wrap1(Q.y - y, F.Y.L, F.Y.h, wy),
-                  dz = wrap1(Q.z - z, F.Z.L, F.Z.h, wz);
-      cand(lsk::dist2(dx, dy, dz), wx == I.x.s && wy == I.y.s && wz == I.z.s, c, (uint32_t)(base + j), id, use);
-    }
-  }
-  return cnt;
-}
+};
 
 }  // namespace periodic
 }  // namespace lsk

@@ -75,10 +75,7 @@ __global__ __launch_bounds__(kWaves * 64) void radius_walk_kernel(const RadArgs 
   const bool live = Q.finite && cut2 > 0.f;
   uint32_t count = 0;
   bool bad = false;
-  // count: the lane took a whole node when the stack stood at cov_sp; everything popped
-  // while the stack is at least that high lies below that node
-  bool cov = false;
-  uint32_t cov_sp = 0;
+  lsk::Cover cov;  // count: the whole node the lane took
   uint32_t s_evals = 0, s_accepts = 0, s_nodes = 0, s_buckets = 0;
 
   if (__ballot(live)) {
@@ -92,24 +89,16 @@ __global__ __launch_bounds__(kWaves * 64) void radius_walk_kernel(const RadArgs 
           s_nodes++;
           bool use = live && !bad && lsk::box_dist2(q, {lo4.x, lo4.y, lo4.z}, {hi4.x, hi4.y, hi4.z}) < cut2;
           if (!kFill) {
-            if (cov && sp < cov_sp) cov = false;
-            use = use && !cov;
-            if (use) {
-              const float fx = fmaxf(fabsf(lo4.x - qx), fabsf(hi4.x - qx));
-              const float fy = fmaxf(fabsf(lo4.y - qy), fabsf(hi4.y - qy));
-              const float fz = fmaxf(fabsf(lo4.z - qz), fabsf(hi4.z - qz));
-              if (lsk::dist2(fx, fy, fz) < cut2) {
-                // the node's points: its buckets, the last one clipped at n
-                const int32_t span_lg = T.depth - lvl;
-                const int64_t first = ((int64_t)node - ((int64_t)1 << lvl)) << span_lg;
-                const int64_t p0 = first * lsk::kBucket;
-                const int64_t p1 = min(T.n, (first + ((int64_t)1 << span_lg)) * lsk::kBucket);
-                if (p1 > p0) count += (uint32_t)(p1 - p0);
-                cov = true;
-                cov_sp = sp;
-                use = false;
-                s_accepts++;
-              }
+            cov.pop(sp);
+            use = use && !cov.on();
+            if (use && lsk::far_dist2(qx, qy, qz, lo4, hi4) < cut2) {
+              // the node's points: its buckets, the last one clipped at n
+              int64_t p0, p1;
+              lsk::node_span(T, node, lvl, p0, p1);
+              if (p1 > p0) count += (uint32_t)(p1 - p0);
+              cov.take(sp);
+              use = false;
+              s_accepts++;
             }
           }
           return use;
@@ -117,13 +106,14 @@ __global__ __launch_bounds__(kWaves * 64) void radius_walk_kernel(const RadArgs 
         // a bucket: the lanes that need it test its points one by one
         [&](uint32_t node, bool use) {
           const bool evals = use;
-          const int cnt = lsk::scan_bucket<kFill>(T, A.perm, node, lane, Q, use, [&](float d2, uint32_t id, bool &use) {
-            if (d2 < cut2) {
+          const int cnt = lsk::scan_bucket(T, node, lane, Q, lsk::OpenDiff{}, lsk::Col<uint32_t, kFill>{A.perm},
+                                           lsk::NoCol{}, use, [&](const auto &c, bool &use) {
+            if (c.d2 < cut2) {
               if (!kFill) {
                 count++;
               } else if (cur < end) {
-                A.out_idx[cur] = (int32_t)id;
-                A.out_dist[cur] = fbits(d2);
+                A.out_idx[cur] = (int32_t)c.a;
+                A.out_dist[cur] = fbits(c.d2);
                 cur++;
               } else {  // more than the count pass saw: stop appending
                 bad = true;
@@ -138,15 +128,7 @@ __global__ __launch_bounds__(kWaves * 64) void radius_walk_kernel(const RadArgs 
 
   if (!kFill) {
     if (Q.valid) A.counts[row] = (int32_t)count;
-    if (A.stats) {
-      const uint32_t e = lsk::wave_sum(s_evals), a = lsk::wave_sum(s_accepts);
-      if (lane == 0) {
-        atomicAdd(&A.stats[0], (unsigned long long)e);
-        atomicAdd(&A.stats[1], (unsigned long long)s_nodes);
-        atomicAdd(&A.stats[2], (unsigned long long)s_buckets);
-        atomicAdd(&A.stats[3], (unsigned long long)a);
-      }
-    }
+    lsk::add_stats<false>(A.stats, lane, s_evals, s_nodes, s_buckets, s_accepts);
   } else if (Q.valid && (bad || cur != end)) {
     atomicAdd(A.err, 1u);
   }

@@ -38,35 +38,6 @@ struct RadVarArgs {
   unsigned long long *stats; // count, optional [4], as radius.hip
 };
 
-// scan_bucket of ball_walk.h with the candidates' own cut2 travelling beside them:
-// cand(d2, cut2 of the point, id, use).
-template <bool kIds, class Cand>
-__device__ __forceinline__ int scan_bucket_cut(const lsk_tree_view &T, const uint32_t *perm, const float *pcut2,
-                                               uint32_t node, int lane, const lsk::GroupQuery &Q, bool &use,
-                                               Cand cand) {
-  const int64_t base = ((int64_t)node - ((int64_t)1 << T.depth)) * lsk::kBucket;
-  if (base >= T.n) return 0;
-  const int cnt = (int)min((int64_t)lsk::kBucket, T.n - base);
-  const int64_t pi = base + lane;
-  float px = 0.f, py = 0.f, pz = 0.f, pc = 0.f;
-  uint32_t pid = 0;
-  if (lane < cnt) {
-    px = T.pts[3 * pi];
-    py = T.pts[3 * pi + 1];
-    pz = T.pts[3 * pi + 2];
-    pc = pcut2[pi];
-    if (kIds) pid = perm[pi];
-  }
-  for (int j = 0; j < cnt; j++) {
-    const float x = lsk::readlane_f(px, j), y = lsk::readlane_f(py, j), z = lsk::readlane_f(pz, j);
-    const float c = lsk::readlane_f(pc, j);
-    uint32_t id = 0;
-    if (kIds) id = (uint32_t)__builtin_amdgcn_readlane((int)pid, j);
-    if (use) cand(lsk::dist2(Q.x - x, Q.y - y, Q.z - z), c, id, use);
-  }
-  return cnt;
-}
-
 template <bool kScatter, bool kFill>
 __global__ __launch_bounds__(kWaves * 64) void radius_var_walk_kernel(const RadVarArgs A) {
   __shared__ uint32_t stk_all[kWaves][lsk::kWalkStack];
@@ -88,9 +59,7 @@ __global__ __launch_bounds__(kWaves * 64) void radius_var_walk_kernel(const RadV
   const bool live = Q.finite && (kScatter || cut2 > 0.f);
   uint32_t count = 0;
   bool bad = false;
-  // gather count: as radius.hip, the lane took a whole node when the stack stood at cov_sp
-  bool cov = false;
-  uint32_t cov_sp = 0;
+  lsk::Cover cov;  // gather count: the whole node the lane took
   uint32_t s_evals = 0, s_accepts = 0, s_nodes = 0, s_buckets = 0;
 
   if (__ballot(live)) {
@@ -122,36 +91,30 @@ __global__ __launch_bounds__(kWaves * 64) void radius_var_walk_kernel(const RadV
           const float c = kScatter ? lo4.w : cut2;
           bool use = live && !bad && lsk::box_dist2(q, {lo4.x, lo4.y, lo4.z}, {hi4.x, hi4.y, hi4.z}) < c;
           if (!kScatter && !kFill) {
-            if (cov && sp < cov_sp) cov = false;
-            use = use && !cov;
-            if (use) {
-              const float fx = fmaxf(fabsf(lo4.x - qx), fabsf(hi4.x - qx));
-              const float fy = fmaxf(fabsf(lo4.y - qy), fabsf(hi4.y - qy));
-              const float fz = fmaxf(fabsf(lo4.z - qz), fabsf(hi4.z - qz));
-              if (lsk::dist2(fx, fy, fz) < cut2) {
-                // the node's points: its buckets, the last one clipped at n
-                const int32_t span_lg = T.depth - lvl;
-                const int64_t first = ((int64_t)node - ((int64_t)1 << lvl)) << span_lg;
-                const int64_t p0 = first * lsk::kBucket;
-                const int64_t p1 = min(T.n, (first + ((int64_t)1 << span_lg)) * lsk::kBucket);
-                if (p1 > p0) count += (uint32_t)(p1 - p0);
-                cov = true;
-                cov_sp = sp;
-                use = false;
-                s_accepts++;
-              }
+            cov.pop(sp);
+            use = use && !cov.on();
+            if (use && lsk::far_dist2(qx, qy, qz, lo4, hi4) < cut2) {
+              // the node's points: its buckets, the last one clipped at n
+              int64_t p0, p1;
+              lsk::node_span(T, node, lvl, p0, p1);
+              if (p1 > p0) count += (uint32_t)(p1 - p0);
+              cov.take(sp);
+              use = false;
+              s_accepts++;
             }
           }
           return use;
         },
         [&](uint32_t node, bool use) {
           const bool evals = use;
+          const lsk::Col<uint32_t, kFill> ids{A.perm};
           int cnt;
-          if (kScatter) {
-            cnt = scan_bucket_cut<kFill>(T, A.perm, A.pcut2, node, lane, Q, use, take);
+          if (kScatter) {  // the candidate's own cutoff travels beside it
+            cnt = lsk::scan_bucket(T, node, lane, Q, lsk::OpenDiff{}, ids, lsk::FloatCol{A.pcut2}, use,
+                                   [&](const auto &c, bool &use) { take(c.d2, c.b, c.a, use); });
           } else {
-            cnt = lsk::scan_bucket<kFill>(T, A.perm, node, lane, Q, use,
-                                          [&](float d2, uint32_t id, bool &use) { take(d2, cut2, id, use); });
+            cnt = lsk::scan_bucket(T, node, lane, Q, lsk::OpenDiff{}, ids, lsk::NoCol{}, use,
+                                   [&](const auto &c, bool &use) { take(c.d2, cut2, c.a, use); });
           }
           if (cnt) s_buckets++;
           if (evals) s_evals += (uint32_t)cnt;
@@ -160,15 +123,7 @@ __global__ __launch_bounds__(kWaves * 64) void radius_var_walk_kernel(const RadV
 
   if (!kFill) {
     if (Q.valid) A.counts[row] = (int32_t)count;
-    if (A.stats) {
-      const uint32_t e = lsk::wave_sum(s_evals), a = lsk::wave_sum(s_accepts);
-      if (lane == 0) {
-        atomicAdd(&A.stats[0], (unsigned long long)e);
-        atomicAdd(&A.stats[1], (unsigned long long)s_nodes);
-        atomicAdd(&A.stats[2], (unsigned long long)s_buckets);
-        atomicAdd(&A.stats[3], (unsigned long long)a);
-      }
-    }
+    lsk::add_stats<false>(A.stats, lane, s_evals, s_nodes, s_buckets, s_accepts);
   } else if (Q.valid && (bad || cur != end)) {
     atomicAdd(A.err, 1u);
   }

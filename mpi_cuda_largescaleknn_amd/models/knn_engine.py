@@ -1688,7 +1688,7 @@ def pair_self_counts(points: torch.Tensor, radii, squared: bool = False, period=
     return pair_query_counts(points, points, radii, squared=squared, period=period, stats=stats)
 
 
-# ---- weighted radius profiles: exact sums of int64 point weights within radii (weighted_profile.hip)
+# ---- weighted radius profiles: exact sums of int64 point weights within radii (radius_profile.hip)
 def _max_abs(w: torch.Tensor) -> int:
     """max |w| of an int64 tensor as a Python int (one small reduction is read; |-2^63| included)."""
     if w.numel() == 0:

@@ -1068,7 +1068,7 @@ def cluster_periodic_gpu(tree: tuple, perm: torch.Tensor, core_sorted: torch.Ten
 
 
 # --------------------------------------------------------------------------- radius profiles
-PROFILE_BINS = 32  # radius_profile.hip kProfileBins: cutoffs per launch, longer lists go in slices
+PROFILE_BINS = 32  # radius_profile.hip CountPolicy::kBins: cutoffs per launch, longer lists go in slices
 
 
 def _profile_cut2s(what: str, cut2s) -> torch.Tensor:
@@ -1107,6 +1107,43 @@ def _profile_stats(what: str, stats: torch.Tensor | None, period, dev: torch.dev
         raise ValueError(f"{what}: stats int64 [{need}] on the tree's device")
 
 
+def _profile_slices(name: str, tree: tuple, qsorted: torch.Tensor, nq: int, cut2s, out_perm: torch.Tensor, period,
+                    stats: torch.Tensor | None, sums: bool, weights: tuple | None = None,
+                    query_weights: torch.Tensor | None = None) -> torch.Tensor:
+    """What the four profile wrappers share: the argument checks, the result, and one call of
+    lsk_hip_<name> per slice of cutoffs. sums: the [B] sums over the queries (with their block
+    workspace) instead of the [nq, B] profile; weights: (wsorted, wpre) of the weighted forms."""
+    what = name + "_gpu"
+    c = _profile_cut2s(what, cut2s)
+    tv = _walk_view(what, tree, qsorted, nq, out_perm)
+    dev = tree[0].device
+    _profile_stats(what, stats, period, dev)
+    if weights is not None:
+        _weighted_args(what, tree, *weights)
+    wq = query_weights
+    if wq is not None and (wq.dtype != torch.int64 or wq.dim() != 1 or wq.shape[0] != nq or not wq.is_contiguous()
+                           or wq.device != dev):
+        raise ValueError(f"{what}: query_weights must be a contiguous int64 [{nq}] tensor on the tree's device")
+    nb = c.shape[0]
+    lib = _native.hip()
+    if sums:
+        res = torch.zeros(nb, dtype=torch.int64, device=dev)
+        ws = torch.empty(int(getattr(lib, f"lsk_hip_{name}_ws_bytes")(int(nq))) // 8, dtype=torch.int64, device=dev)
+        tail = (_ptr(ws), _ptr(res)) if weights is None else (_ptr(wq), _ptr(ws), _ptr(res))
+    else:
+        res = torch.empty((nq, nb), dtype=torch.int32 if weights is None else torch.int64, device=dev)
+        tail = (_ptr(res), nb)
+    cdev = c.to(dev)
+    per = None if period is None else _period_c(period)
+    fn = getattr(lib, "lsk_hip_" + name)
+    width = PROFILE_BINS if weights is None else int(lib.lsk_hip_weighted_profile_bins())
+    for col0 in range(0, nb, width):
+        m = min(width, nb - col0)
+        check(fn(C.byref(tv), _ptr(qsorted), int(nq), cdev.data_ptr() + 4 * col0, m, per, _ptr(out_perm),
+                 *(_ptr(t) for t in weights or ()), *tail, col0, _ptr(stats), _stream(tree[0])), name)
+    return res
+
+
 def radius_profile_gpu(tree: tuple, qsorted: torch.Tensor, nq: int, cut2s, out_perm: torch.Tensor,
                        period: tuple[float, float, float] | None = None,
                        stats: torch.Tensor | None = None) -> torch.Tensor:
@@ -1116,21 +1153,7 @@ def radius_profile_gpu(tree: tuple, qsorted: torch.Tensor, nq: int, cut2s, out_p
     result. tree / qsorted / out_perm as for radius_count_gpu; cut2s: B >= 1 ascending squared
     cutoffs on the host (within the period's bound: the caller checks). stats: optional zeroed
     int64 [4] (period: [RADIUS_PERIODIC_STATS]), summed over the slices."""
-    c = _profile_cut2s("radius_profile_gpu", cut2s)
-    tv = _walk_view("radius_profile_gpu", tree, qsorted, nq, out_perm)
-    dev = tree[0].device
-    _profile_stats("radius_profile_gpu", stats, period, dev)
-    nb = c.shape[0]
-    out = torch.empty((nq, nb), dtype=torch.int32, device=dev)
-    cdev = c.to(dev)
-    per = None if period is None else _period_c(period)
-    lib = _native.hip()
-    for col0 in range(0, nb, PROFILE_BINS):
-        m = min(PROFILE_BINS, nb - col0)
-        check(lib.lsk_hip_radius_profile(C.byref(tv), _ptr(qsorted), int(nq), cdev.data_ptr() + 4 * col0, m, per,
-                                         _ptr(out_perm), _ptr(out), nb, col0, _ptr(stats), _stream(tree[0])),
-              "radius_profile")
-    return out
+    return _profile_slices("radius_profile", tree, qsorted, nq, cut2s, out_perm, period, stats, sums=False)
 
 
 def pair_counts_gpu(tree: tuple, qsorted: torch.Tensor, nq: int, cut2s, out_perm: torch.Tensor,
@@ -1140,22 +1163,7 @@ def pair_counts_gpu(tree: tuple, qsorted: torch.Tensor, nq: int, cut2s, out_perm
     tree's device, the column sums of radius_profile_gpu, without its [nq, B] array: every block
     writes one row of bin sums into a workspace of nq / 256 rows, which one small kernel adds.
     Arguments as for radius_profile_gpu."""
-    c = _profile_cut2s("pair_counts_gpu", cut2s)
-    tv = _walk_view("pair_counts_gpu", tree, qsorted, nq, out_perm)
-    dev = tree[0].device
-    _profile_stats("pair_counts_gpu", stats, period, dev)
-    nb = c.shape[0]
-    sums = torch.zeros(nb, dtype=torch.int64, device=dev)
-    cdev = c.to(dev)
-    per = None if period is None else _period_c(period)
-    lib = _native.hip()
-    ws = torch.empty(int(lib.lsk_hip_pair_counts_ws_bytes(int(nq))) // 8, dtype=torch.int64, device=dev)
-    for col0 in range(0, nb, PROFILE_BINS):
-        m = min(PROFILE_BINS, nb - col0)
-        check(lib.lsk_hip_pair_counts(C.byref(tv), _ptr(qsorted), int(nq), cdev.data_ptr() + 4 * col0, m, per,
-                                      _ptr(out_perm), _ptr(ws), _ptr(sums), col0, _ptr(stats), _stream(tree[0])),
-              "pair_counts")
-    return sums
+    return _profile_slices("pair_counts", tree, qsorted, nq, cut2s, out_perm, period, stats, sums=True)
 
 
 # --------------------------------------------------------------------------- weighted radius profiles
@@ -1201,7 +1209,7 @@ def weighted_pair_sums_cpu(points: torch.Tensor, queries: torch.Tensor, cut2s, w
 
 
 def weighted_profile_bins() -> int:
-    """Cutoffs per launch of weighted_profile.hip (kWeightedBins); longer lists go in slices."""
+    """Cutoffs per launch of radius_profile.hip's weight policy; longer lists go in slices."""
     return int(_native.hip().lsk_hip_weighted_profile_bins())
 
 
@@ -1216,63 +1224,26 @@ def weighted_profile_gpu(tree: tuple, qsorted: torch.Tensor, nq: int, cut2s, out
                          wsorted: torch.Tensor, wpre: torch.Tensor,
                          period: tuple[float, float, float] | None = None,
                          stats: torch.Tensor | None = None) -> torch.Tensor:
-    """The weighted radius profile (weighted_profile.hip) on the current stream: int64 [nq, B] in
-    query order, column b = the sum of the weights of the points with dist2 < cut2s[b], from one
-    walk per slice of up to weighted_profile_bins() cutoffs. wsorted: int64 [n], the weights in
-    the tree's curve order; wpre: int64 [n + 1], their exclusive prefix sum. The caller
-    guarantees max|w| * n < 2^62. Everything else as for radius_profile_gpu."""
-    c = _profile_cut2s("weighted_profile_gpu", cut2s)
-    tv = _walk_view("weighted_profile_gpu", tree, qsorted, nq, out_perm)
-    dev = tree[0].device
-    _profile_stats("weighted_profile_gpu", stats, period, dev)
-    _weighted_args("weighted_profile_gpu", tree, wsorted, wpre)
-    nb = c.shape[0]
-    out = torch.empty((nq, nb), dtype=torch.int64, device=dev)
-    cdev = c.to(dev)
-    per = None if period is None else _period_c(period)
-    lib = _native.hip()
-    width = int(lib.lsk_hip_weighted_profile_bins())
-    for col0 in range(0, nb, width):
-        m = min(width, nb - col0)
-        check(lib.lsk_hip_weighted_profile(C.byref(tv), _ptr(qsorted), int(nq), cdev.data_ptr() + 4 * col0, m, per,
-                                           _ptr(out_perm), _ptr(wsorted), _ptr(wpre), _ptr(out), nb, col0,
-                                           _ptr(stats), _stream(tree[0])),
-              "weighted_profile")
-    return out
+    """The weighted radius profile (radius_profile.hip, the weight policy) on the current stream:
+    int64 [nq, B] in query order, column b = the sum of the weights of the points with dist2 <
+    cut2s[b], from one walk per slice of up to weighted_profile_bins() cutoffs. wsorted: int64 [n],
+    the weights in the tree's curve order; wpre: int64 [n + 1], their exclusive prefix sum. The
+    caller guarantees max|w| * n < 2^62. Everything else as for radius_profile_gpu."""
+    return _profile_slices("weighted_profile", tree, qsorted, nq, cut2s, out_perm, period, stats, sums=False,
+                           weights=(wsorted, wpre))
 
 
 def weighted_pair_sums_gpu(tree: tuple, qsorted: torch.Tensor, nq: int, cut2s, out_perm: torch.Tensor,
                            wsorted: torch.Tensor, wpre: torch.Tensor, query_weights: torch.Tensor | None = None,
                            period: tuple[float, float, float] | None = None,
                            stats: torch.Tensor | None = None) -> torch.Tensor:
-    """The weighted pair sums (weighted_profile.hip, sum mode) on the current stream: int64 [B] on
-    the tree's device, the sum over the queries of query_weights[q] (int64 [nq] in query order;
-    None: 1) times row q of weighted_profile_gpu, without its [nq, B] array. The caller
-    guarantees (sum |w|) * (sum |query_weights|) < 2^63. Arguments as for weighted_profile_gpu."""
-    c = _profile_cut2s("weighted_pair_sums_gpu", cut2s)
-    tv = _walk_view("weighted_pair_sums_gpu", tree, qsorted, nq, out_perm)
-    dev = tree[0].device
-    _profile_stats("weighted_pair_sums_gpu", stats, period, dev)
-    _weighted_args("weighted_pair_sums_gpu", tree, wsorted, wpre)
-    wq = query_weights
-    if wq is not None and (wq.dtype != torch.int64 or wq.dim() != 1 or wq.shape[0] != nq or not wq.is_contiguous()
-                           or wq.device != dev):
-        raise ValueError(f"weighted_pair_sums_gpu: query_weights must be a contiguous int64 [{nq}] tensor on the "
-                         f"tree's device")
-    nb = c.shape[0]
-    sums = torch.zeros(nb, dtype=torch.int64, device=dev)
-    cdev = c.to(dev)
-    per = None if period is None else _period_c(period)
-    lib = _native.hip()
-    width = int(lib.lsk_hip_weighted_profile_bins())
-    ws = torch.empty(int(lib.lsk_hip_weighted_pair_sums_ws_bytes(int(nq))) // 8, dtype=torch.int64, device=dev)
-    for col0 in range(0, nb, width):
-        m = min(width, nb - col0)
-        check(lib.lsk_hip_weighted_pair_sums(C.byref(tv), _ptr(qsorted), int(nq), cdev.data_ptr() + 4 * col0, m, per,
-                                             _ptr(out_perm), _ptr(wsorted), _ptr(wpre), _ptr(wq), _ptr(ws),
-                                             _ptr(sums), col0, _ptr(stats), _stream(tree[0])),
-              "weighted_pair_sums")
-    return sums
+    """The weighted pair sums (radius_profile.hip, the weight policy in sum mode) on the current
+    stream: int64 [B] on the tree's device, the sum over the queries of query_weights[q] (int64
+    [nq] in query order; None: 1) times row q of weighted_profile_gpu, without its [nq, B] array.
+    The caller guarantees (sum |w|) * (sum |query_weights|) < 2^63. Arguments as for
+    weighted_profile_gpu."""
+    return _profile_slices("weighted_pair_sums", tree, qsorted, nq, cut2s, out_perm, period, stats, sums=True,
+                           weights=(wsorted, wpre), query_weights=query_weights)
 
 
 # --------------------------------------------------------------------------- periodic k-NN

@@ -5,8 +5,8 @@ the workload of an LDS counter run that compares the two walk kernels:
     rocprofv3 --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAVES -d OUT -o run \
         --output-format csv -- python scripts/weighted_profile_lds.py [--points 2e6]
 
-OUT/run_counter_collection.csv then holds one row per kernel and counter (radius_profile_walk_kernel
-and weighted_profile_walk_kernel, <false, false> and <true, false>). 16 log-spaced radii from r/8 to
+OUT/run_counter_collection.csv then holds one row per kernel and counter (radius_profile_walk_kernel,
+CountPolicy and WeightPolicy, <false, false> and <true, false>). 16 log-spaced radii from r/8 to
 r, r for ~100 neighbours, the points as their own queries; figures in docs/ARCHITECTURE.md.
 """
 from __future__ import annotations
