@@ -47,4 +47,4 @@ from .models.knn_engine import (KnnConfig, build_index, cluster_labels, cluster_
                                 pair_counts, pair_query_counts, pair_self_counts, PointWeights,
                                 prepare_point_weights, fixed_point_weights, weighted_profile, weighted_query_profile,
                                 weighted_self_profile, weighted_pair_sums, weighted_pair_query_sums,
-                                weighted_pair_self_sums)
+                                weighted_pair_self_sums, mst_edges, mst_points, mst_labels)

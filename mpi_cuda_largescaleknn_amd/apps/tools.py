@@ -29,6 +29,9 @@
            [--period L | Lx,Ly,Lz]
            -> hipKNN_cluster's PREFIX.labels and PREFIX.core against the brute-force oracle, every
               point (at most 65536: the oracle visits every pair)
+    python -m mpi_cuda_largescaleknn_amd.apps.tools mcheck in.float3 PREFIX [--core-k K]
+           -> hipKNN_mst's PREFIX.mst.rows and PREFIX.mst.d2 against the brute-force oracle, every
+              edge (at most 65536 points: the oracle visits every pair)
     python -m mpi_cuda_largescaleknn_amd.apps.tools wrap in.float3 out.float3 --period L | Lx,Ly,Lz [--origin O | Ox,Oy,Oz]
            -> the points brought into one period [O, O + L) per finite axis (knn_engine.wrap_points)
     python -m mpi_cuda_largescaleknn_amd.apps.tools cat prefix P out.float  (concatenate per-rank outputs)
@@ -375,6 +378,41 @@ def ccheck(a) -> int:
     return 0 if bad_c.numel() + bad_l.numel() == 0 else 1
 
 
+def mcheck(a) -> int:
+    pts = io.read_points(a.inp)
+    n = pts.shape[0]
+    if n > CCHECK_MAX:
+        print(f"mcheck: {n} points, more than {CCHECK_MAX}: the oracle is quadratic (it visits every pair of "
+              "points); check a smaller set")
+        return 1
+    if a.core_k < 0:
+        print("mcheck: --core-k must be at least 1")
+        return 1
+    rows = io.read_array(a.prefix + ".mst.rows", torch.int32)
+    d2 = io.read_array(a.prefix + ".mst.d2", torch.float32)
+    if rows.shape[0] != 2 * d2.shape[0]:
+        print(f"size mismatch: {rows.shape[0]} row entries for {d2.shape[0]} weights")
+        return 1
+    rows = rows.view(-1, 2)
+    core = None
+    if a.core_k:  # the oracle's squared K-th distances, 0 for a point that is no vertex
+        core = K.kth_cpu(pts, pts, a.core_k, math.inf)
+        core[~torch.isfinite(pts).all(dim=1)] = 0.0
+        if not bool(torch.isfinite(core).all()):
+            print(f"mcheck: --core-k {a.core_k} exceeds the number of finite points")
+            return 1
+    ref_r, ref_d = K.mst_cpu(pts, core)
+    if ref_d.shape[0] != d2.shape[0]:
+        print(f"checked {n} points: {d2.shape[0]} edges, the oracle has {ref_d.shape[0]}")
+        return 1
+    bad = ((rows != ref_r).any(dim=1) | (d2.view(torch.int32) != ref_d.view(torch.int32))).nonzero().flatten()
+    print(f"checked {n} points: {ref_d.shape[0]} edges, {bad.numel()} edge mismatches")
+    for i in bad[:10].tolist():
+        print(f"EDGE {i:012d} = ({int(rows[i, 0])}, {int(rows[i, 1])}) d2 {d2[i].item()!r} "
+              f"(oracle ({int(ref_r[i, 0])}, {int(ref_r[i, 1])}) d2 {ref_d[i].item()!r})")
+    return 0 if bad.numel() == 0 else 1
+
+
 def wrap(a) -> int:
     pts = io.read_points(a.inp)
     try:
@@ -459,6 +497,10 @@ def main(argv=None) -> int:
     p.add_argument("--min-pts", type=int, default=1)
     p.add_argument("--squared", action="store_true", help="-r is the squared cutoff")
     add_period_option(p)
+    p = sub.add_parser("mcheck")
+    p.add_argument("inp")
+    p.add_argument("prefix", help="the -o PREFIX of hipKNN_mst")
+    p.add_argument("--core-k", type=int, default=0, metavar="K", help="the --core-k of the run")
     p = sub.add_parser("wrap")
     p.add_argument("inp")
     p.add_argument("out")
@@ -475,7 +517,8 @@ def main(argv=None) -> int:
     a = ap.parse_args(argv)
     if a.cmd == "wrap" and a.period is None:
         ap.error("wrap: --period is required")
-    return {"gen": gen, "split": split, "check": check, "rcheck": rcheck, "ccheck": ccheck, "wrap": wrap, "cat": cat,
+    return {"gen": gen, "split": split, "check": check, "rcheck": rcheck, "ccheck": ccheck, "mcheck": mcheck, "wrap": wrap,
+            "cat": cat,
             "cmp": cmp, "fixweights": fixweights}[a.cmd](a)
 
 

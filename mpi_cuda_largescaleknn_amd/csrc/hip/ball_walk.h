@@ -256,14 +256,17 @@ __device__ __forceinline__ void add_stats(unsigned long long *stats, int lane, u
 // needs the node (`use`); a node no lane needs is dropped. Inner nodes are then expanded with
 // `keep` (see expand), buckets go to on_bucket(node, use). Without kTestInner an inner
 // node's own box is never loaded: its descendants were culled against the group already.
+// ball_walk_from walks the subtree of `root` alone (a node that covers at least one bucket):
+// the stack argument of walk_stack holds for it a fortiori, a subtree being no deeper than
+// the tree. mst.hip walks the siblings of a bucket's ancestors one after the other with it.
 template <bool kTestInner, class Keep, class OnNode, class OnBucket>
-__device__ __forceinline__ void ball_walk(const lsk_tree_view &T, uint32_t *stk, int lane, Keep keep,
-                                          OnNode on_node, OnBucket on_bucket) {
+__device__ __forceinline__ void ball_walk_from(const lsk_tree_view &T, uint32_t *stk, int lane, uint32_t root,
+                                               Keep keep, OnNode on_node, OnBucket on_bucket) {
   const int32_t depth = T.depth;
   const int64_t nb = (T.n + kBucket - 1) / kBucket;
   const float4 *nodes = (const float4 *)T.nodes;
   uint32_t sp = 1;
-  if (lane == 0) stk[0] = 1u;
+  if (lane == 0) stk[0] = root;
   __builtin_amdgcn_wave_barrier();
   while (sp > 0) {
     sp--;
@@ -281,6 +284,12 @@ __device__ __forceinline__ void ball_walk(const lsk_tree_view &T, uint32_t *stk,
     else
       on_bucket(node, use);
   }
+}
+
+template <bool kTestInner, class Keep, class OnNode, class OnBucket>
+__device__ __forceinline__ void ball_walk(const lsk_tree_view &T, uint32_t *stk, int lane, Keep keep,
+                                          OnNode on_node, OnBucket on_bucket) {
+  ball_walk_from<kTestInner>(T, stk, lane, 1u, keep, on_node, on_bucket);
 }
 
 }  // namespace lsk

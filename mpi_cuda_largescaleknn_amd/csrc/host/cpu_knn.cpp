@@ -328,6 +328,77 @@ extern "C" void lsk_cpu_cluster(const float *pts, int64_t n, float cut2, int min
   });
 }
 
+// Euclidean minimum spanning tree by brute force: Prim over all pairs of finite points under the
+// strict total order (bits of w, lo, hi), O(n²) time and O(n) memory. The order being total,
+// the MST is unique: any correct algorithm yields this edge set. Edges come out sorted by key.
+extern "C" int64_t lsk_cpu_mst(const float *pts, int64_t n, const float *core, int32_t *rows, float *d2) {
+  const vec3f *P = (const vec3f *)pts;
+  struct Key {
+    uint64_t wlo;  // bits of w << 32 | lo
+    uint32_t hi;
+    bool operator<(const Key &o) const { return wlo != o.wlo ? wlo < o.wlo : hi < o.hi; }
+  };
+  std::vector<int32_t> v;  // the vertices outside the tree
+  for (int64_t i = 0; i < n; i++)
+    if (std::isfinite(P[i].x) && std::isfinite(P[i].y) && std::isfinite(P[i].z)) v.push_back((int32_t)i);
+  if (v.size() < 2) return 0;
+  auto key = [&](int32_t a, int32_t b) {
+    float w = lsk::dist2(P[a], P[b]);
+    if (core) w = std::max(std::max(w, core[a] + 0.f), core[b] + 0.f);  // (+ 0.f: -0 has other bits)
+    return Key{((uint64_t)lsk::fbits(w) << 32) | (uint32_t)std::min(a, b), (uint32_t)std::max(a, b)};
+  };
+  std::vector<Key> best(v.size(), Key{~0ull, ~0u});  // beside v: the smallest edge into the tree
+  std::vector<Key> out;
+  int32_t last = v[0];  // the vertex that joined the tree last
+  v[0] = v.back();
+  v.pop_back();
+  best.pop_back();
+  while (!v.empty()) {
+    size_t arg = 0;
+    for (size_t i = 0; i < v.size(); i++) {
+      const Key k = key(v[i], last);
+      if (k < best[i]) best[i] = k;
+      if (best[i] < best[arg]) arg = i;
+    }
+    out.push_back(best[arg]);
+    last = v[arg];
+    v[arg] = v.back();
+    best[arg] = best.back();
+    v.pop_back();
+    best.pop_back();
+  }
+  std::sort(out.begin(), out.end());
+  for (size_t i = 0; i < out.size(); i++) {
+    rows[2 * i] = (int32_t)(uint32_t)out[i].wlo;
+    rows[2 * i + 1] = (int32_t)out[i].hi;
+    d2[i] = lsk::bitsf((uint32_t)(out[i].wlo >> 32));
+  }
+  return (int64_t)out.size();
+}
+
+// The components of the edges with d2 < cut2 (strict) over rows 0 .. n - 1, each labelled by its
+// smallest row: the host form of mst_labels.
+extern "C" int lsk_cpu_mst_labels(const int32_t *rows, const float *d2, int64_t m, float cut2, int64_t n,
+                                  int32_t *labels) {
+  for (int64_t i = 0; i < n; i++) labels[i] = (int32_t)i;
+  auto find = [&](int32_t x) {
+    while (labels[x] != x) {
+      labels[x] = labels[labels[x]];
+      x = labels[x];
+    }
+    return x;
+  };
+  for (int64_t i = 0; i < m; i++) {
+    if (!(d2[i] < cut2)) continue;
+    const int64_t a0 = rows[2 * i], b0 = rows[2 * i + 1];
+    if (a0 < 0 || b0 < 0 || a0 >= n || b0 >= n) return 1;
+    const int32_t a = find((int32_t)a0), b = find((int32_t)b0);
+    if (a != b) labels[std::max(a, b)] = std::min(a, b);
+  }
+  for (int64_t i = 0; i < n; i++) labels[i] = find((int32_t)i);
+  return 0;
+}
+
 // ---- periodic box: the minimum image of the difference, written out literally ----------------
 // Per axis d = q - p; h = 0.5f * L; d > h: d - L; d < -h: d + L (L = inf never wraps); then the
 // canonical dist2. Symmetric in its bits (fl(q - p) = -fl(p - q), mirrored branches).

@@ -106,7 +106,16 @@ void lsk_cpu_radius_var_fill(const float *pts, int64_t n, const float *qry, int6
 // (dist2 bits, row) among those with dist2 < cut2, and without one -1, or i when min_pts = 1.
 void lsk_cpu_cluster(const float *pts, int64_t n, float cut2, int min_pts, int32_t *labels, uint8_t *core,
                      int nthreads);
-// The three above under a period (three values > 0, +inf = open axis): dist2 is replaced by the
+// Euclidean minimum spanning tree by brute force (Prim over all pairs). Vertices: the points with
+// finite coordinates. Weight of {a, b}: w = dist2, or with core (optional, [n] floats >= 0)
+// max(dist2, core[a], core[b]). Edges are ordered by (bits of w, lo, hi), lo < hi the rows: a
+// strict total order, so the tree is unique. rows (int32 [m][2], (lo, hi)) and d2 ([m], w) receive
+// the m = max(finite points - 1, 0) edges ascending by that key (room for n - 1); returns m.
+int64_t lsk_cpu_mst(const float *pts, int64_t n, const float *core, int32_t *rows, float *d2);
+// labels[i] (int32 [n]) = the smallest row of i's component under the edges with d2 < cut2
+// (strict); returns non-zero when an edge names a row outside [0, n).
+int lsk_cpu_mst_labels(const int32_t *rows, const float *d2, int64_t m, float cut2, int64_t n, int32_t *labels);
+// The radius search and the clustering above under a period (three values > 0, +inf = open axis): dist2 is replaced by the
 // minimum image of the difference — per axis d = q - p, h = 0.5f * L, d > h: d - L, d < -h:
 // d + L, in float32 and in this order — then the canonical dist2. qcut2 (optional, [nq])
 // replaces cut2 per query.

@@ -2135,6 +2135,176 @@ def cluster_points(points: torch.Tensor, eps: float, min_pts: int = 1, squared: 
     return cluster_labels(build_index(points), eps, min_pts, squared=squared, stats=stats)
 
 
+# ------------------------------------------------------------------ minimum spanning tree
+# the device error word of the last mst_edges / device mst_labels run (tests: always 0)
+LAST_MST_ERRORS = [0]
+_MST_STATS = ("mst_evals", "mst_nodes", "mst_buckets", None, "mst_cas_retries")
+
+
+def _mst_core(what: str, core_d2, n: int, device: torch.device) -> torch.Tensor | None:
+    """The checked core distances: float32 [n] on `device`, every entry finite and >= 0 (one small
+    device reduction is read), with -0 made +0 (the max of the contract compares bits)."""
+    if core_d2 is None:
+        return None
+    if not isinstance(core_d2, torch.Tensor) or core_d2.dtype != torch.float32 or core_d2.dim() != 1 \
+            or core_d2.shape[0] != n:
+        got = f"{core_d2.dtype} {tuple(core_d2.shape)}" if isinstance(core_d2, torch.Tensor) else type(core_d2).__name__
+        raise ValueError(f"{what}: core_d2 must be a float32 [{n}] tensor (got {got})")
+    if core_d2.device != device:
+        raise ValueError(f"{what}: core_d2 on {core_d2.device}, the index on {device}")
+    if n and not bool(((core_d2 >= 0) & (core_d2 < math.inf)).all()):  # (a NaN fails the comparison too)
+        raise ValueError(f"{what}: every entry of core_d2 must be finite and >= 0")
+    return core_d2.contiguous() + 0.0
+
+
+def mst_core_d2(index: LocalIndex, k: int) -> torch.Tensor:
+    """Core distances for mst_edges: float32 [n] in the order of the indexed array's rows, the
+    squared distance from every point to its k-th nearest neighbour (itself counted: query's own
+    value, 1 <= k <= the number of finite points), and 0 for a point with a NaN or infinite
+    coordinate, which is no vertex."""
+    if isinstance(k, bool) or int(k) != k or k < 1:
+        raise ValueError(f"mst_core_d2: k must be an integer >= 1 (got {k})")
+    n = index.n
+    out = torch.zeros(n, dtype=torch.float32, device=index.device)
+    if n == 0:
+        return out
+    d2 = query(index, KnnConfig(k=int(k)), radius_hint(index.box, n, int(k)))
+    d2 = torch.where(torch.isfinite(index.pts[:n]).all(dim=1), d2[:n], torch.zeros_like(d2[:n]))
+    out[index.perm[:n].long()] = d2
+    return out
+
+
+def _empty_mst(device: torch.device) -> tuple[torch.Tensor, torch.Tensor]:
+    return (torch.empty((0, 2), dtype=torch.int32, device=device), torch.empty(0, dtype=torch.float32, device=device))
+
+
+def mst_edges(index: LocalIndex, core_d2: torch.Tensor | None = None,
+              stats: KnnStats | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """The Euclidean minimum spanning tree of the points of `index`: (rows int32 [m, 2], d2
+    float32 [m]), the single-linkage hierarchy at every linking length at once.
+
+    Vertices are the points with finite coordinates (a point with a NaN or infinite coordinate
+    is in no edge), m = max(their number - 1, 0). The weight of the pair {a, b} is w = dist2(a,
+    b), the canonical float32 squared distance every other function here compares; with core_d2
+    (float32 [n] on the index's device, in the order of the indexed array's rows, every entry
+    finite and >= 0, e.g. the squared k-th neighbour distances) it is the mutual-reachability
+    weight max(dist2(a, b), core_d2[a], core_d2[b]), the input of HDBSCAN. Edges are ordered by
+    the key (bits of w, lo, hi), lo < hi the two rows, compared lexicographically: a strict total
+    order, so the tree is unique, and exact copies and lattice ties are decided by it alone.
+    Each row of `rows` is (lo, hi), d2 holds w, both ascending by the key. The result depends
+    on the inputs alone: not on the index's internal order, the grid, the number of rounds or
+    the order in which the device's atomics land, and it equals K.mst_cpu bit for bit.
+
+    Weights stay squared: a cut at eps compares d2 < cut2_of(eps) exactly as radius_counts does
+    (mst_labels), and a square root would lose that.
+
+    The device runs Boruvka rounds over the bucket tree (mst.hip) in O(n) memory, with one
+    small host read per round (the edge counter) after one for the number of finite points; the
+    components at least halve per round. A wrong core_d2 raises ValueError before any walk, as
+    does an index built in a rotated frame or keyed along a line. A round beyond ceil(log2(n)),
+    a final edge count other than m or a non-zero error word raise NativeError (a bug, no
+    fallback). `stats` receives mst_rounds, mst_evals / _nodes / _buckets / _cas_retries and
+    mst_components, the component count before every round. There is no period."""
+    if index.qrot is not None or index.line:
+        raise ValueError("mst_edges: an index built in a rotated frame or keyed along a line cannot serve "
+                         "(build_index(points) without a frame)")
+    n, dev = index.n, index.device
+    core = _mst_core("mst_edges", core_d2, n, dev)
+    if n == 0:
+        return _empty_mst(dev)
+    if not K.is_gpu(index.pts):
+        KERNELS_USED.add("cpu")
+        return K.mst_cpu(_input_order(index), core)
+    perm = index.perm[:n]
+    raw = torch.zeros(K.MST_STATS, dtype=torch.int64, device=dev) if stats is not None else None
+    state = K.MstState(index.tree(), index.perm, core[perm.long()].contiguous() if core is not None else None, raw)
+    KERNELS_USED.add("mst")
+    n_finite = int(torch.isfinite(index.pts[:n]).all(dim=1).sum().item())
+    want = max(n_finite - 1, 0)
+    max_rounds = max(n_finite - 1, 0).bit_length()  # ceil(log2(n_finite))
+    done, rounds, comps = 0, 0, []
+    while done < want:
+        if rounds == max_rounds:
+            raise NativeError(f"mst_edges: {n_finite - done} components left after {rounds} rounds "
+                              "(they must at least halve per round: a bug)")
+        comps.append(n_finite - done)
+        state.round()
+        rounds += 1
+        now = int(state.count.item()) & 0xFFFFFFFF  # the round's host read
+        if now <= done:
+            break
+        done = now
+    LAST_MST_ERRORS[0] = int(state.err.item()) & 0xFFFFFFFF
+    if LAST_MST_ERRORS[0]:
+        raise NativeError(f"mst_edges: error word {LAST_MST_ERRORS[0]} (an invariant of the union-find or of "
+                          "the rounds is broken: a bug)")
+    if done != want:
+        raise NativeError(f"mst_edges: {done} edges for {n_finite} finite points (a bug)")
+    if stats is not None:
+        for nm, v in zip(_MST_STATS, raw.cpu().tolist()):
+            if nm:
+                stats.counters[nm] = stats.counters.get(nm, 0) + int(v)
+        stats.counters["mst_rounds"] = rounds
+        stats.counters["mst_components"] = comps
+    rows, d2 = state.rows[:want], state.d2[:want]
+    # ascending by (bits of w, lo, hi): a stable sort by hi, then one by (bits of w << 32 | lo)
+    order = torch.sort(rows[:, 1], stable=True).indices
+    key = (d2.view(torch.int32).long() << 32) | rows[:, 0].long()
+    order = order[torch.sort(key[order], stable=True).indices]
+    return rows[order].contiguous(), d2[order].contiguous()
+
+
+def mst_points(points: torch.Tensor, core_d2: torch.Tensor | None = None,
+               stats: KnnStats | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """mst_edges over an index built once from `points` (float32 [n, 3]), in the points' own
+    frame."""
+    if points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32:
+        raise ValueError("mst_points: points must be a float32 [n, 3] tensor")
+    if points.shape[0] == 0:  # nothing to index
+        _mst_core("mst_points", core_d2, 0, points.device)
+        return _empty_mst(points.device)
+    return mst_edges(build_index(points), core_d2, stats=stats)
+
+
+def mst_labels(rows: torch.Tensor, d2: torch.Tensor, n: int, eps: float, squared: bool = False) -> torch.Tensor:
+    """The single-linkage clusters at one linking length from the tree of mst_edges: labels
+    int32 [n], the connected components of the edges with d2 < cut2_of(eps) (the strict float32
+    comparison of radius_counts; squared=True: eps is the squared cutoff itself), each labelled
+    by its smallest row; a row in no such edge is labelled by itself. For a tree built without
+    core_d2 this equals cluster_labels(index, eps, min_pts=1)[0] bit for bit: two points are in
+    one friends-of-friends group iff a path of pairs below the cutoff joins them, iff the path
+    between them in the minimum spanning tree stays below it. The weights are squared distances
+    and must stay so: the cut compares them with the squared cutoff. Device tensors run the edge
+    hook of mst.hip and the label passes of cluster.hip (one host read, the error word), CPU
+    tensors the host runtime."""
+    try:
+        cut2 = _radius_cut2("mst_labels", eps, squared)
+    except ValueError:
+        raise ValueError(f"mst_labels: eps must be >= 0 (got {eps})") from None
+    if isinstance(n, bool) or int(n) != n or n < 0:
+        raise ValueError(f"mst_labels: n must be an integer >= 0 (got {n})")
+    n = int(n)
+    if not isinstance(rows, torch.Tensor) or not isinstance(d2, torch.Tensor) or rows.dtype != torch.int32 \
+            or d2.dtype != torch.float32 or rows.dim() != 2 or rows.shape[1] != 2 or d2.dim() != 1 \
+            or rows.shape[0] != d2.shape[0]:
+        raise ValueError("mst_labels: rows must be an int32 [m, 2] tensor and d2 a float32 [m] tensor")
+    if rows.device != d2.device:
+        raise ValueError(f"mst_labels: rows on {rows.device}, d2 on {d2.device}")
+    if d2.shape[0] > max(n - 1, 0):
+        raise ValueError(f"mst_labels: {d2.shape[0]} edges are no forest over {n} rows")
+    if n == 0:
+        return torch.empty(0, dtype=torch.int32, device=d2.device)
+    if not K.is_gpu(d2):
+        return K.mst_labels_cpu(rows, d2, n, cut2)
+    labels, err = K.mst_labels_gpu(rows, d2, n, cut2)
+    KERNELS_USED.update(("mst", "cluster"))
+    LAST_MST_ERRORS[0] = int(err.item()) & 0xFFFFFFFF  # the only host read
+    if LAST_MST_ERRORS[0]:
+        raise NativeError(f"mst_labels: error word {LAST_MST_ERRORS[0]} (an edge names a row outside [0, {n}), or "
+                          "the union-find's invariant is broken)")
+    return labels
+
+
 def compact_labels(labels: torch.Tensor) -> tuple[torch.Tensor, int]:
     """(dense int32 labels, number of clusters): the clusters of cluster_labels numbered 0, 1,
     ... by ascending label (the smallest row of their core points); -1 stays -1."""

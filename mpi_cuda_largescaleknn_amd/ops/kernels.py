@@ -894,6 +894,102 @@ def cluster_gpu(tree: tuple, perm: torch.Tensor, core_sorted: torch.Tensor, cut2
     return labels, err
 
 
+# --------------------------------------------------------------------------- minimum spanning tree
+def mst_cpu(points: torch.Tensor, core_d2: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """CPU oracle of the Euclidean minimum spanning tree (Prim over all pairs): (rows int32 [m,
+    2], d2 float32 [m]). Vertices are the points with finite coordinates, m = max(their number -
+    1, 0); the weight of {a, b} is w = dist2(a, b), with core_d2 (float32 [n], every entry finite
+    and >= 0) max(dist2(a, b), core_d2[a], core_d2[b]); edges are ordered by (bits of w, lo, hi)
+    with lo < hi the two rows, a strict total order, so the tree is unique. Each row of `rows` is
+    (lo, hi), d2 holds w, both ascending by that key."""
+    pts = points.contiguous().float().cpu()
+    n = pts.shape[0]
+    core = None
+    if core_d2 is not None:
+        core = core_d2.contiguous().float().cpu()
+        if core.dim() != 1 or core.shape[0] != n or not bool((torch.isfinite(core) & (core >= 0)).all()):
+            raise ValueError("mst_cpu: core_d2 must hold n finite entries >= 0")
+    rows = torch.empty((max(n - 1, 0), 2), dtype=torch.int32)
+    d2 = torch.empty(max(n - 1, 0), dtype=torch.float32)
+    m = int(_native.host().lsk_cpu_mst(_ptr(pts), n, _ptr(core), _ptr(rows), _ptr(d2)))
+    return rows[:m].contiguous(), d2[:m].contiguous()
+
+
+def mst_labels_cpu(rows: torch.Tensor, d2: torch.Tensor, n: int, cut2: float) -> torch.Tensor:
+    """labels int32 [n]: the smallest row of every row's component under the edges with d2 < cut2."""
+    rows = rows.contiguous()
+    d2 = d2.contiguous()
+    labels = torch.empty(n, dtype=torch.int32)
+    if _native.host().lsk_cpu_mst_labels(_ptr(rows), _ptr(d2), d2.shape[0], C.c_float(cut2), n, _ptr(labels)):
+        raise ValueError(f"mst_labels: an edge names a row outside [0, {n})")
+    return labels
+
+
+MST_STATS = 5  # mst.hip: distance evaluations, nodes popped, buckets scanned, unused, CAS retries
+
+
+class MstState:
+    """The device buffers of the Boruvka rounds over one tree (mst.hip): O(n)."""
+
+    def __init__(self, tree: tuple, perm: torch.Tensor, core_sorted: torch.Tensor | None,
+                 stats: torch.Tensor | None = None):
+        pts, nodes, qnodes, n, depth = tree
+        dev = pts.device
+        if perm.dtype != torch.int32 or perm.numel() < n or not perm.is_contiguous() or perm.device != dev:
+            raise ValueError("mst_gpu: perm int32 [n], contiguous, on the tree's device")
+        if core_sorted is not None and (core_sorted.dtype != torch.float32 or core_sorted.numel() != n
+                                        or not core_sorted.is_contiguous() or core_sorted.device != dev):
+            raise ValueError("mst_gpu: core_sorted float32 [n], contiguous, on the tree's device")
+        if stats is not None and (stats.dtype != torch.int64 or stats.numel() < MST_STATS or stats.device != dev):
+            raise ValueError(f"mst_gpu: stats int64 [{MST_STATS}] on the tree's device")
+        self.tv = TreeView(_ptr(pts), _ptr(nodes), _ptr(qnodes), n, depth, 0)
+        self.keep = (pts, nodes, qnodes, perm, core_sorted, stats)  # (the view holds raw pointers)
+        self.n = n
+        self.parent = torch.arange(n, dtype=torch.int32, device=dev)
+        self.comp = torch.empty(n, dtype=torch.int32, device=dev)
+        self.ncomp = torch.empty(2 << depth, dtype=torch.int32, device=dev)
+        self.best = torch.empty(n, dtype=torch.int64, device=dev)
+        self.best_pos = torch.empty(n, dtype=torch.int32, device=dev)
+        self.cmin = torch.empty(n, dtype=torch.int64, device=dev)
+        self.chi = torch.empty(n, dtype=torch.int32, device=dev)
+        self.rows = torch.empty((n, 2), dtype=torch.int32, device=dev)
+        self.d2 = torch.empty(n, dtype=torch.float32, device=dev)
+        self.count = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.err = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def round(self) -> None:
+        """One Boruvka round on the current stream (no host read)."""
+        pts, _, _, perm, core, stats = self.keep
+        check(_native.hip().lsk_hip_mst_round(
+            C.byref(self.tv), _ptr(perm), _ptr(core), _ptr(self.parent), _ptr(self.comp), _ptr(self.ncomp),
+            _ptr(self.best), _ptr(self.best_pos), _ptr(self.cmin), _ptr(self.chi), _ptr(self.rows), _ptr(self.d2),
+            _ptr(self.count), _ptr(self.err), _ptr(stats), _stream(pts)), "mst_round")
+
+
+def mst_labels_gpu(rows: torch.Tensor, d2: torch.Tensor, n: int, cut2: float) -> tuple[torch.Tensor, torch.Tensor]:
+    """(labels int32 [n], err int32 [1]) of device edges (rows int32 [m, 2], d2 float32 [m], n >=
+    1): the edge hook of mst.hip, then the label passes of cluster.hip over the rows themselves
+    (identity perm, every row a core point, a row without an edge its own label)."""
+    dev = d2.device
+    m = d2.shape[0]
+    rows = rows.contiguous()
+    d2 = d2.contiguous()
+    lib, st = _native.hip(), _stream(d2)
+    parent = torch.arange(n, dtype=torch.int32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    check(lib.lsk_hip_mst_cut(_ptr(rows), _ptr(d2), m, C.c_float(cut2), n, _ptr(parent), _ptr(err), st), "mst_cut")
+    ident = torch.arange(n, dtype=torch.int32, device=dev)
+    core = torch.ones(n, dtype=torch.uint8, device=dev)
+    root = torch.empty(n, dtype=torch.int32, device=dev)
+    minrow = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    labels = torch.empty(n, dtype=torch.int32, device=dev)
+    # the label passes read the view's n alone; its pointers only have to be non-null
+    tv = TreeView(_ptr(ident), _ptr(ident), None, n, int(lib.lsk_hip_tree_depth(n)), 0)
+    check(lib.lsk_hip_cluster_label(C.byref(tv), _ptr(ident), _ptr(core), _ptr(parent), 1, _ptr(root),
+                                    _ptr(minrow), _ptr(labels), _ptr(err), st), "cluster_label")
+    return labels, err
+
+
 # --------------------------------------------------------------------------- periodic box
 RADIUS_PERIODIC_STATS = 5  # periodic.hip: the four of radius.hip and the image walks
 
