@@ -144,6 +144,8 @@ def _declare_host(lib: C.CDLL) -> None:
     lib.lsk_cpu_cluster.restype = None
     lib.lsk_cpu_mst.argtypes = [vp, i64, vp, vp, vp]
     lib.lsk_cpu_mst.restype = i64
+    lib.lsk_cpu_mst_periodic.argtypes = [vp, i64, vp, vp, vp, vp]
+    lib.lsk_cpu_mst_periodic.restype = i64
     lib.lsk_cpu_mst_labels.argtypes = [vp, vp, i64, C.c_float, i64, vp]
     lib.lsk_cpu_mst_labels.restype = i32
     lib.lsk_cpu_radius_periodic_count.argtypes = [vp, i64, vp, i64, C.c_float, vp, vp, vp, i32]
@@ -222,6 +224,8 @@ def _declare_hip(lib: C.CDLL) -> None:
         "lsk_hip_cluster_border": ([C.POINTER(TreeView), vp, vp, C.c_float, vp, vp, vp, vp, vp], i32),
         "lsk_hip_cluster_init": ([C.POINTER(TreeView), vp, vp, C.c_float, vp, vp, vp], i32),
         "lsk_hip_mst_round": ([C.POINTER(TreeView), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp], i32),
+        "lsk_hip_mst_periodic_round": ([C.POINTER(TreeView), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                        vp], i32),
         "lsk_hip_mst_cut": ([vp, vp, i64, C.c_float, i64, vp, vp, vp], i32),
         "lsk_hip_radius_periodic_count": ([C.POINTER(TreeView), vp, i64, C.c_float, vp, vp, vp, vp, vp, vp], i32),
         "lsk_hip_radius_periodic_fill": ([C.POINTER(TreeView), vp, vp, i64, C.c_float, vp, vp, vp, vp, vp, vp, vp,

@@ -1,7 +1,7 @@
 """hipKNN_mst — Euclidean minimum spanning tree: single linkage at every linking length.
 
     hipKNN_mst <points.float3> -o <PREFIX> [--core-k K] [--cut EPS [--squared]]
-               [--device auto|cuda|cpu] [--stats f.json] [-v]
+               [--period L | Lx,Ly,Lz] [--device auto|cuda|cpu] [--stats f.json] [-v]
 
 The vertices are the points with finite coordinates; the weight of a pair is its squared
 distance dist2 (float32, the value hipKNN_radius compares), and edges are ordered by (bits of
@@ -16,7 +16,12 @@ distance from p to its K-th nearest neighbour (itself counted): the tree HDBSCAN
 --cut EPS (--squared: EPS is the squared cutoff) also writes PREFIX.labels, one int32 per point
 row: the smallest row of the point's component under the edges with weight < EPS².
 
-One process, one device; no periodic box.
+--period L or Lx,Ly,Lz (inf: an open axis): the box is periodic and dist2 is that of the
+minimum image of the difference (hipKNN_radius --period), with no bound on an edge's length;
+the --core-k distances are the periodic ones and the --cut groups those of hipKNN_cluster
+--period at the same EPS. Bring the points into one period first (lsknn_tools wrap).
+
+One process, one device.
 """
 from __future__ import annotations
 
@@ -32,6 +37,7 @@ from ..models import knn_engine as E
 from ..parallel import launch as L
 from ..utils import io
 from .query import _device
+from .radius import add_period_option
 
 
 def parse(argv: list[str]) -> argparse.Namespace:
@@ -43,6 +49,7 @@ def parse(argv: list[str]) -> argparse.Namespace:
                     help="mutual-reachability weights from the squared K-th neighbour distances")
     ap.add_argument("--cut", type=float, default=None, metavar="EPS", help="also write PREFIX.labels at this cutoff")
     ap.add_argument("--squared", action="store_true", help="--cut is the squared cutoff")
+    add_period_option(ap)
     ap.add_argument("--device", choices=["auto", "cuda", "cpu"], default="auto")
     ap.add_argument("--stats", default="", help="write run statistics to this JSON file")
     ap.add_argument("-v", dest="verbose", action="store_true")
@@ -70,8 +77,8 @@ def main(argv: list[str] | None = None) -> int:
     sync()
     t1 = time.perf_counter()
     try:
-        core = E.mst_core_d2(index, a.core_k) if a.core_k else None
-        rows, d2 = E.mst_edges(index, core, stats=stats)
+        core = E.mst_core_d2(index, a.core_k, period=a.period) if a.core_k else None
+        rows, d2 = E.mst_edges(index, core, stats=stats, period=a.period)
         labels = E.mst_labels(rows, d2, index.n, a.cut, squared=a.squared) if a.cut is not None else None
     except ValueError as e:
         sys.stderr.write(f"hipKNN_mst: {e}\n")
@@ -95,6 +102,8 @@ def main(argv: list[str] | None = None) -> int:
         rec = {"n": index.n, "edges": int(d2.numel()), "core_k": a.core_k, "cut": a.cut, "squared": a.squared,
                "device": str(dev), "index_s": t1 - t0, "mst_s": t2 - t1, "kernels": E.kernels_used(),
                "mst": stats.counters}
+        if a.period is not None:
+            rec["period"] = list(a.period)
         with open(a.stats, "w") as f:
             json.dump(rec, f, indent=1)
     return 0

@@ -29,7 +29,7 @@
            [--period L | Lx,Ly,Lz]
            -> hipKNN_cluster's PREFIX.labels and PREFIX.core against the brute-force oracle, every
               point (at most 65536: the oracle visits every pair)
-    python -m mpi_cuda_largescaleknn_amd.apps.tools mcheck in.float3 PREFIX [--core-k K]
+    python -m mpi_cuda_largescaleknn_amd.apps.tools mcheck in.float3 PREFIX [--core-k K] [--period L | Lx,Ly,Lz]
            -> hipKNN_mst's PREFIX.mst.rows and PREFIX.mst.d2 against the brute-force oracle, every
               edge (at most 65536 points: the oracle visits every pair)
     python -m mpi_cuda_largescaleknn_amd.apps.tools wrap in.float3 out.float3 --period L | Lx,Ly,Lz [--origin O | Ox,Oy,Oz]
@@ -396,12 +396,13 @@ def mcheck(a) -> int:
     rows = rows.view(-1, 2)
     core = None
     if a.core_k:  # the oracle's squared K-th distances, 0 for a point that is no vertex
-        core = K.kth_cpu(pts, pts, a.core_k, math.inf)
+        core = K.kth_cpu(pts, pts, a.core_k, math.inf) if a.period is None else \
+            K.kth_periodic_cpu(pts, pts, a.core_k, math.inf, a.period)
         core[~torch.isfinite(pts).all(dim=1)] = 0.0
         if not bool(torch.isfinite(core).all()):
             print(f"mcheck: --core-k {a.core_k} exceeds the number of finite points")
             return 1
-    ref_r, ref_d = K.mst_cpu(pts, core)
+    ref_r, ref_d = K.mst_cpu(pts, core) if a.period is None else K.mst_periodic_cpu(pts, a.period, core)
     if ref_d.shape[0] != d2.shape[0]:
         print(f"checked {n} points: {d2.shape[0]} edges, the oracle has {ref_d.shape[0]}")
         return 1
@@ -501,6 +502,7 @@ def main(argv=None) -> int:
     p.add_argument("inp")
     p.add_argument("prefix", help="the -o PREFIX of hipKNN_mst")
     p.add_argument("--core-k", type=int, default=0, metavar="K", help="the --core-k of the run")
+    add_period_option(p)
     p = sub.add_parser("wrap")
     p.add_argument("inp")
     p.add_argument("out")

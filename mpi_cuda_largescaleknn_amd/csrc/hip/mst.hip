@@ -41,6 +41,32 @@
 // Every component picks its smallest outgoing edge under a strict total order, so the picked
 // edges are MST edges, form no cycle, and the components at least halve per round.
 //
+// Under a period (lsk_hip_mst_periodic_round) the weight of a pair is pd2, the minimum image of
+// periodic.hip, symmetric in its bits, and only step 3 changes (mst_nearest_periodic_kernel,
+// whose second argument MstPeriod carries the period). Every pair has exactly one wrap vector in {-1, 0, +1}^3, and the
+// walk visits the images one after the other; a candidate counts in the image that is its wrap
+// vector (`mine` of ImageDiff) and nowhere else, so the minimum over images is the minimum over
+// pairs. The 64-bit key argument above does not ask which image a pair came from.
+//   Image 0 first, in the open order and under the open culls: a pair of wrap vector 0 has pd2 =
+//   the open-box dist2 bit for bit, of which box_dist2 / box_box_dist2 are lower bounds as before.
+//   After it nearly every lane holds a bound.
+//   Then every other image the group can take (image_of), one ball walk from the root each, the
+//   boxes tested against the shifted query by the slackened gaps image_box_dist2 (group) and
+//   image_point_dist2 (lane). periodic.hip proves that these are lower bounds of pd2 for every
+//   pair of the image inside the box ("The cull is conservative"); that proof argues per pair and
+//   never uses cut2 <= fl(h h): only the whole-box acceptance and the tight nodes of periodic.hip
+//   need that bound, and the nearest walk has neither, so an edge may be as long as it likes and
+//   the coordinates need not lie inside one period. A node is dropped for a lane as in image 0:
+//   ncomp[node] its own component (nothing foreign inside, whatever the shift), or the bits of
+//   max(gap, core[q]) above its best w; equality is kept.
+//   What image 0 knows does not carry over: the own bucket and the two curve neighbours are
+//   ordinary buckets of a shifted walk (their pairs with that wrap vector were not counted in
+//   image 0; with n <= 64 every wrapped pair is such a pair), and a lane may arrive without any
+//   candidate (every foreign point wraps): maxbw is then all ones and the walk runs unbounded.
+//   The image loop and maxbw are wave-uniform; every walk starts and ends with an empty stack, so
+//   the kWalkStack words of a wave serve all of them. L = inf never wraps and takes no image but
+//   0: an open period gives the open result bit for bit.
+//
 // As in cluster.hip no lane waits on another lane, wave or flag, and no loop is unbounded:
 // unite's retries strictly lower a position, a parent chain strictly decreases (a chain that
 // does not bumps the error word and gives up: the host raises), and every tree walk pops a
@@ -48,9 +74,11 @@
 #include <type_traits>
 
 #include "cluster_uf.h"
+#include "periodic_image.h"
 
 namespace {
 
+using namespace lsk::periodic;
 using lsk::fbits;
 using lsk::load_own;
 using lsk::unite;
@@ -82,7 +110,30 @@ struct MstArgs {
   float *ew;                   // [n] edges: w
   uint32_t *count;             // edges written so far
   uint32_t *err;
-  unsigned long long *stats;   // optional [5]: distance evaluations, nodes popped, buckets scanned, 0, CAS retries
+  unsigned long long *stats;   // optional [5]: distance evaluations, nodes popped, buckets scanned, image
+                               // walks beyond image 0 (periodic), CAS retries
+};
+
+// What the nearest walk knows about the box. OpenBox: nothing, the difference of a scan is the
+// open one. PeriodicBox: the period (the kernel's second argument), the group's frame and image 0.
+struct OpenBox {
+  static constexpr bool kPeriodic = false;
+  __device__ __forceinline__ void init(const lsk_tree_view &, const lsk::box3f &) {}
+  __device__ __forceinline__ lsk::OpenDiff diff0() const { return {}; }
+};
+struct PeriodicBox {
+  static constexpr bool kPeriodic = true;
+  float L[3];
+  Frame F;
+  Image I0;
+  __device__ __forceinline__ void init(const lsk_tree_view &T, const lsk::box3f &gb) {
+    F = make_frame(T, L, gb);
+    image_of(F.X, F.Y, F.Z, 13, I0);
+  }
+  __device__ __forceinline__ ImageDiff diff0() const { return {F, I0}; }
+};
+struct MstPeriod {
+  float L[3];
 };
 
 __device__ __forceinline__ uint32_t wave_min_u(uint32_t v) {
@@ -162,8 +213,9 @@ __global__ __launch_bounds__(256) void mst_level_kernel(const MstArgs A, int lev
   A.ncomp[node] = v;
 }
 
-template <bool kCore>
-__global__ __launch_bounds__(kWaves * 64) void mst_nearest_kernel(const MstArgs A) {
+template <bool kCore, class Box>
+__device__ __forceinline__ void mst_nearest(const MstArgs &A, Box &B) {
+  constexpr bool kPeriodic = Box::kPeriodic;
   __shared__ uint32_t stk_all[kWaves][lsk::kWalkStack];
   const int wid = threadIdx.x >> 6;
   const int lane = lsk::lane_id();
@@ -178,7 +230,7 @@ __global__ __launch_bounds__(kWaves * 64) void mst_nearest_kernel(const MstArgs 
   if (kCore && live) kq = A.core[pos_q];
   unsigned long long best = kNoKey;
   uint32_t best_pos = 0;
-  uint32_t s_evals = 0, s_nodes = 0, s_buckets = 0;
+  uint32_t s_evals = 0, s_nodes = 0, s_buckets = 0, s_images = 0;
   if (__ballot(live)) {
     const lsk::box3f gb = lsk::group_box(Q, live);
     const lsk::vec3f q{Q.x, Q.y, Q.z};
@@ -190,26 +242,35 @@ __global__ __launch_bounds__(kWaves * 64) void mst_nearest_kernel(const MstArgs 
     // (wave-uniform) the largest bound of the live lanes, as bits; all ones while a lane has none
     uint32_t maxbw = 0xffffffffu;
     using CoreCol = std::conditional_t<kCore, lsk::FloatCol, lsk::NoCol>;
-    auto on_bucket = [&](uint32_t node, bool use) {
-      const bool evals = use;
-      CoreCol cc{};
-      if constexpr (kCore) cc.p = A.core;
-      const int cnt = lsk::scan_bucket(T, node, lane, Q, lsk::OpenDiff{}, CompRowCol{A.comp, A.perm}, cc, use,
-                                       [&](const auto &c, bool &) {
-                                         if (c.a.comp != cq && c.a.comp != kWild) {
-                                           float w = c.d2;
-                                           if constexpr (kCore) w = fmaxf(fmaxf(w, kq), c.b);
-                                           const unsigned long long key = ((unsigned long long)fbits(w) << 32) | c.a.row;
-                                           if (key < best) {
-                                             best = key;
-                                             best_pos = c.pos;
+    // the bucket scan of a walk under the difference of its image (open box: every candidate is
+    // `mine`). A maker and not one more call level around the scan: the open form then compiles
+    // to the code it had before there was a periodic one.
+    auto scan_under = [&](const auto diff) {
+      return [&, diff](uint32_t node, bool use) {
+        const bool evals = use;
+        CoreCol cc{};
+        if constexpr (kCore) cc.p = A.core;
+        const int cnt = lsk::scan_bucket(T, node, lane, Q, diff, CompRowCol{A.comp, A.perm}, cc, use,
+                                         [&](const auto &c, bool &) {
+                                           if (c.mine && c.a.comp != cq && c.a.comp != kWild) {
+                                             float w = c.d2;
+                                             if constexpr (kCore) w = fmaxf(fmaxf(w, kq), c.b);
+                                             const unsigned long long key = ((unsigned long long)fbits(w) << 32) | c.a.row;
+                                             if (key < best) {
+                                               best = key;
+                                               best_pos = c.pos;
+                                             }
                                            }
-                                         }
-                                       });
-      if (cnt) s_buckets++;
-      if (evals) s_evals += (uint32_t)cnt;
-      maxbw = wave_max_u(live ? (uint32_t)(best >> 32) : 0u);
+                                         });
+        if (cnt) s_buckets++;
+        if (evals) s_evals += (uint32_t)cnt;
+        maxbw = wave_max_u(live ? (uint32_t)(best >> 32) : 0u);
+      };
     };
+    // image 0: the pairs of wrap vector 0, whose pd2 is the open-box dist2, in the open order
+    // and under the open culls
+    B.init(T, gb);
+    auto on_bucket = scan_under(B.diff0());
     on_bucket(leaf, live);
     if (left) on_bucket(left, live);
     if (right) on_bucket(right, live);
@@ -230,12 +291,49 @@ __global__ __launch_bounds__(kWaves * 64) void mst_nearest_kernel(const MstArgs 
       if (first >= nb) continue;  // (covers no bucket: its slot of the node array is not a box)
       lsk::ball_walk_from<true>(T, stk_all[wid], lane, sib, keep, on_node, on_bucket);
     }
+    if constexpr (kPeriodic) {
+      // every other image the group can take, one walk from the root each: the own bucket and
+      // the curve neighbours are ordinary buckets here, and a lane may still have no bound
+      const Frame &F = B.F;
+      for (int im = 0; im < 27; im++) {  // (wave-uniform)
+        Image I;
+        if (im == 13 || !image_of(F.X, F.Y, F.Z, im, I)) continue;
+        if (fbits(image_box_dist2(gb, F.rlo, F.rhi, I)) > maxbw) continue;
+        s_images++;
+        lsk::ball_walk<true>(
+            T, stk_all[wid], lane,
+            [&](const float4 &lo4, const float4 &hi4) { return fbits(image_box_dist2(gb, lo4, hi4, I)) <= maxbw; },
+            [&](uint32_t node, int32_t, uint32_t, const float4 &lo4, const float4 &hi4) {
+              s_nodes++;
+              const uint32_t nc = A.ncomp[node];  // (wave-uniform)
+              float bd2 = image_point_dist2(Q, lo4, hi4, I);
+              if (kCore) bd2 = fmaxf(bd2, kq);
+              return live && nc != kNone && nc != cq && fbits(bd2) <= (uint32_t)(best >> 32);
+            },
+            scan_under(ImageDiff{F, I}));
+      }
+    }
   }
   if (Q.valid) {
     A.best[pos_q] = best;
     A.best_pos[pos_q] = best_pos;
   }
-  lsk::add_stats<false>(A.stats, lane, s_evals, s_nodes, s_buckets, 0u);
+  lsk::add_stats<false>(A.stats, lane, s_evals, s_nodes, s_buckets, lane == 0 ? s_images : 0u);
+}
+
+template <bool kCore>
+__global__ __launch_bounds__(kWaves * 64) void mst_nearest_kernel(const MstArgs A) {
+  OpenBox B;
+  mst_nearest<kCore>(A, B);
+}
+
+template <bool kCore>
+__global__ __launch_bounds__(kWaves * 64) void mst_nearest_periodic_kernel(const MstArgs A, const MstPeriod P) {
+  PeriodicBox B;
+  B.L[0] = P.L[0];
+  B.L[1] = P.L[1];
+  B.L[2] = P.L[2];
+  mst_nearest<kCore>(A, B);
 }
 
 // The first two fields of the lane's candidate edge (bits of w << 32 | lo) and the third.
@@ -322,21 +420,31 @@ __global__ __launch_bounds__(256) void mst_cut_kernel(const int32_t *__restrict_
 
 }  // namespace
 
-extern "C" int lsk_hip_mst_round(const lsk_tree_view *tree, const uint32_t *perm, const float *core,
-                                 uint32_t *parent, uint32_t *comp, uint32_t *ncomp, unsigned long long *best,
-                                 uint32_t *best_pos, unsigned long long *cmin, uint32_t *chi, int32_t *erows,
-                                 float *ew, uint32_t *count, uint32_t *err, unsigned long long *stats,
-                                 void *stream) {
+namespace {
+
+// One round; period: null (open box) or three values > 0 (+inf: open axis).
+int mst_round(const char *what, const lsk_tree_view *tree, const uint32_t *perm, const float *core,
+              const float *period, uint32_t *parent, uint32_t *comp, uint32_t *ncomp, unsigned long long *best,
+              uint32_t *best_pos, unsigned long long *cmin, uint32_t *chi, int32_t *erows, float *ew,
+              uint32_t *count, uint32_t *err, unsigned long long *stats, void *stream) {
   if (!lsk_tree_ok(tree)) {
-    lsk::set_last_error("mst_round: tree view incomplete (1 <= n < 2^31, depth = tree_depth(n))");
+    lsk::set_last_error(std::string(what) + ": tree view incomplete (1 <= n < 2^31, depth = tree_depth(n))");
     return 1;
   }
   if (!perm || !parent || !comp || !ncomp || !best || !best_pos || !cmin || !chi || !erows || !ew || !count ||
       !err) {
-    lsk::set_last_error("mst_round: null argument");
+    lsk::set_last_error(std::string(what) + ": null argument");
     return 1;
   }
   MstArgs A{};
+  MstPeriod P{};
+  for (int a = 0; period && a < 3; a++) {
+    if (!(period[a] > 0.f)) {
+      lsk::set_last_error(std::string(what) + ": period must be three values > 0 (+inf: open axis)");
+      return 1;
+    }
+    P.L[a] = period[a];
+  }
   A.T = *tree;
   A.perm = perm;
   A.core = core;
@@ -364,10 +472,16 @@ extern "C" int lsk_hip_mst_round(const lsk_tree_view *tree, const uint32_t *perm
     LSK_CHECK_LAUNCH("mst level");
   }
   const unsigned walk_blocks = lsk_blocks((n + lsk::kBucket - 1) / lsk::kBucket, kWaves);
-  if (core)
+  if (period) {
+    if (core)
+      mst_nearest_periodic_kernel<true><<<walk_blocks, kWaves * 64, 0, st>>>(A, P);
+    else
+      mst_nearest_periodic_kernel<false><<<walk_blocks, kWaves * 64, 0, st>>>(A, P);
+  } else if (core) {
     mst_nearest_kernel<true><<<walk_blocks, kWaves * 64, 0, st>>>(A);
-  else
+  } else {
     mst_nearest_kernel<false><<<walk_blocks, kWaves * 64, 0, st>>>(A);
+  }
   LSK_CHECK_LAUNCH("mst nearest");
   mst_min1_kernel<<<per_pos, 256, 0, st>>>(A);
   LSK_CHECK_LAUNCH("mst min1");
@@ -376,6 +490,30 @@ extern "C" int lsk_hip_mst_round(const lsk_tree_view *tree, const uint32_t *perm
   mst_emit_kernel<<<per_pos, 256, 0, st>>>(A);
   LSK_CHECK_LAUNCH("mst emit");
   return 0;
+}
+
+}  // namespace
+
+extern "C" int lsk_hip_mst_round(const lsk_tree_view *tree, const uint32_t *perm, const float *core,
+                                 uint32_t *parent, uint32_t *comp, uint32_t *ncomp, unsigned long long *best,
+                                 uint32_t *best_pos, unsigned long long *cmin, uint32_t *chi, int32_t *erows,
+                                 float *ew, uint32_t *count, uint32_t *err, unsigned long long *stats,
+                                 void *stream) {
+  return mst_round("mst_round", tree, perm, core, nullptr, parent, comp, ncomp, best, best_pos, cmin, chi, erows, ew,
+                   count, err, stats, stream);
+}
+
+extern "C" int lsk_hip_mst_periodic_round(const lsk_tree_view *tree, const uint32_t *perm, const float *core,
+                                          const float *period, uint32_t *parent, uint32_t *comp, uint32_t *ncomp,
+                                          unsigned long long *best, uint32_t *best_pos, unsigned long long *cmin,
+                                          uint32_t *chi, int32_t *erows, float *ew, uint32_t *count, uint32_t *err,
+                                          unsigned long long *stats, void *stream) {
+  if (!period) {
+    lsk::set_last_error("mst_periodic_round: period must be three values > 0 (+inf: open axis)");
+    return 1;
+  }
+  return mst_round("mst_periodic_round", tree, perm, core, period, parent, comp, ncomp, best, best_pos, cmin, chi,
+                   erows, ew, count, err, stats, stream);
 }
 
 extern "C" int lsk_hip_mst_cut(const int32_t *rows, const float *d2, int64_t m, float cut2, int64_t n,

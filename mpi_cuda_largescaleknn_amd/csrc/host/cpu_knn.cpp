@@ -331,7 +331,11 @@ extern "C" void lsk_cpu_cluster(const float *pts, int64_t n, float cut2, int min
 // Euclidean minimum spanning tree by brute force: Prim over all pairs of finite points under the
 // strict total order (bits of w, lo, hi), O(n²) time and O(n) memory. The order being total,
 // the MST is unique: any correct algorithm yields this edge set. Edges come out sorted by key.
-extern "C" int64_t lsk_cpu_mst(const float *pts, int64_t n, const float *core, int32_t *rows, float *d2) {
+// pair(p, q): the squared distance of two points (open box: dist2; periodic: the minimum image).
+namespace {
+
+template <class Pair>
+int64_t mst_prim(const float *pts, int64_t n, const float *core, int32_t *rows, float *d2, Pair pair) {
   const vec3f *P = (const vec3f *)pts;
   struct Key {
     uint64_t wlo;  // bits of w << 32 | lo
@@ -343,7 +347,7 @@ extern "C" int64_t lsk_cpu_mst(const float *pts, int64_t n, const float *core, i
     if (std::isfinite(P[i].x) && std::isfinite(P[i].y) && std::isfinite(P[i].z)) v.push_back((int32_t)i);
   if (v.size() < 2) return 0;
   auto key = [&](int32_t a, int32_t b) {
-    float w = lsk::dist2(P[a], P[b]);
+    float w = pair(P[a], P[b]);
     if (core) w = std::max(std::max(w, core[a] + 0.f), core[b] + 0.f);  // (+ 0.f: -0 has other bits)
     return Key{((uint64_t)lsk::fbits(w) << 32) | (uint32_t)std::min(a, b), (uint32_t)std::max(a, b)};
   };
@@ -374,6 +378,12 @@ extern "C" int64_t lsk_cpu_mst(const float *pts, int64_t n, const float *core, i
     d2[i] = lsk::bitsf((uint32_t)(out[i].wlo >> 32));
   }
   return (int64_t)out.size();
+}
+
+}  // namespace
+
+extern "C" int64_t lsk_cpu_mst(const float *pts, int64_t n, const float *core, int32_t *rows, float *d2) {
+  return mst_prim(pts, n, core, rows, d2, [](const vec3f &a, const vec3f &b) { return lsk::dist2(a, b); });
 }
 
 // The components of the edges with d2 < cut2 (strict) over rows 0 .. n - 1, each labelled by its
@@ -418,6 +428,13 @@ inline float pdist2(const vec3f &q, const vec3f &p, const float *L) {
 }
 
 }  // namespace
+
+// lsk_cpu_mst with the pair weight pd2 (symmetric in its bits, so the weight of a pair is well
+// defined); no bound on an edge's length.
+extern "C" int64_t lsk_cpu_mst_periodic(const float *pts, int64_t n, const float *core, const float *period,
+                                        int32_t *rows, float *d2) {
+  return mst_prim(pts, n, core, rows, d2, [=](const vec3f &a, const vec3f &b) { return pdist2(a, b, period); });
+}
 
 // lsk_cpu_radius_count under a period; qcut2 (optional, [nq]) replaces cut2 per query.
 extern "C" void lsk_cpu_radius_periodic_count(const float *pts, int64_t n, const float *qry, int64_t nq, float cut2,

@@ -112,6 +112,10 @@ void lsk_cpu_cluster(const float *pts, int64_t n, float cut2, int min_pts, int32
 // strict total order, so the tree is unique. rows (int32 [m][2], (lo, hi)) and d2 ([m], w) receive
 // the m = max(finite points - 1, 0) edges ascending by that key (room for n - 1); returns m.
 int64_t lsk_cpu_mst(const float *pts, int64_t n, const float *core, int32_t *rows, float *d2);
+// lsk_cpu_mst under a period (three values > 0, +inf = open axis): dist2 is replaced by the
+// minimum image of the difference (below), whatever the length of an edge.
+int64_t lsk_cpu_mst_periodic(const float *pts, int64_t n, const float *core, const float *period, int32_t *rows,
+                             float *d2);
 // labels[i] (int32 [n]) = the smallest row of i's component under the edges with d2 < cut2
 // (strict); returns non-zero when an edge names a row outside [0, n).
 int lsk_cpu_mst_labels(const int32_t *rows, const float *d2, int64_t m, float cut2, int64_t n, int32_t *labels);

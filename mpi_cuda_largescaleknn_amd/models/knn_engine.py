@@ -948,6 +948,42 @@ def _knn_period(what: str, index: LocalIndex | None, period) -> tuple | None:
 LAST_PERIODIC_KNN_ERRORS = [0]
 
 
+def _flagged_slices(what: str, index: LocalIndex, per: tuple, cfg: KnnConfig, qsorted: torch.Tensor,
+                    d2: torch.Tensor, max_pairs: int, raw: torch.Tensor | None = None) -> tuple:
+    """The flag and count passes of the periodic k-NN (knn_periodic.hip) over the open-box k-th
+    squared distances d2 (sorted-query order), and the slicing of the flagged rows: (cutq, qlist,
+    pairs, slices) with qlist the flagged sorted queries (int32, ascending), pairs their total
+    count and slices a list of (qlist[a:b], offsets int64 [b - a + 1], total, longest), each the
+    longest run of rows within max_pairs pairs (a single row with more raises ValueError). Two
+    host reads: the list's length and the counts' prefix sum."""
+    nq = d2.shape[0]
+    tree = index.tree()
+    cutq, flags = K.pknn_flag_gpu(tree, qsorted, nq, d2, cfg.cut2, per)
+    KERNELS_USED.add("knn_periodic")
+    qlist = torch.nonzero(flags).view(-1).int()  # (host read: the list's length)
+    m = qlist.numel()
+    if m == 0:
+        return cutq, qlist, 0, []
+    counts = K.pknn_count_gpu(tree, qsorted, nq, qlist, cutq, per, stats=raw)
+    cum = torch.zeros(m + 1, dtype=torch.int64, device=index.device)
+    torch.cumsum(counts, 0, dtype=torch.int64, out=cum[1:])
+    hcum = cum.cpu()  # (host read: decides the slices)
+    hcounts = hcum[1:] - hcum[:-1]
+    if int(hcounts.max()) > max_pairs:
+        raise ValueError(f"{what}: a query has {int(hcounts.max())} points within its open-box k-th "
+                         f"distance, more than max_pairs = {max_pairs}; raise max_pairs")
+    slices = []
+    a = 0
+    while a < m:
+        # the longest run of rows from a within max_pairs pairs (at least one: checked above)
+        b = int(torch.searchsorted(hcum, hcum[a] + max_pairs, right=True)) - 1
+        b = max(a + 1, min(b, m))
+        slices.append((qlist[a:b].contiguous(), (cum[a:b + 1] - cum[a]).contiguous(), int(hcum[b] - hcum[a]),
+                       int(hcounts[a:b].max())))
+        a = b
+    return cutq, qlist, int(hcum[m]), slices
+
+
 def _periodic_knn(index: LocalIndex, per: tuple, cfg: KnnConfig, qsorted: torch.Tensor, qperm: torch.Tensor,
                   d2: torch.Tensor, out: torch.Tensor, out_idx: torch.Tensor | None, out_dist: torch.Tensor | None,
                   stats: KnnStats | None, max_pairs: int, flagged: torch.Tensor | None) -> None:
@@ -957,42 +993,21 @@ def _periodic_knn(index: LocalIndex, per: tuple, cfg: KnnConfig, qsorted: torch.
     they run a periodic radius search with that bound, in slices of at most max_pairs pairs,
     and the first k of each sorted row overwrite their entries of out / out_idx / out_dist."""
     nq = d2.shape[0]
-    tree = index.tree()
-    cutq, flags = K.pknn_flag_gpu(tree, qsorted, nq, d2, cfg.cut2, per)
-    KERNELS_USED.add("knn_periodic")
-    qlist = torch.nonzero(flags).view(-1).int()  # (host read: the list's length)
-    m = qlist.numel()
+    raw = torch.zeros(K.RADIUS_PERIODIC_STATS, dtype=torch.int64, device=index.device) if stats is not None else None
+    LAST_PERIODIC_KNN_ERRORS[0] = 0
+    cutq, qlist, pairs, slices = _flagged_slices("periodic k-NN", index, per, cfg, qsorted, d2, max_pairs, raw)
     if flagged is not None:
         flagged[qperm[qlist.long()].long()] = True
-    raw = torch.zeros(K.RADIUS_PERIODIC_STATS, dtype=torch.int64, device=index.device) if stats is not None else None
-    pairs = 0
-    LAST_PERIODIC_KNN_ERRORS[0] = 0
-    if m:
-        counts = K.pknn_count_gpu(tree, qsorted, nq, qlist, cutq, per, stats=raw)
-        cum = torch.zeros(m + 1, dtype=torch.int64, device=index.device)
-        torch.cumsum(counts, 0, dtype=torch.int64, out=cum[1:])
-        hcum = cum.cpu()  # (host read: decides the slices)
-        pairs = int(hcum[m])
-        hcounts = hcum[1:] - hcum[:-1]
-        if int(hcounts.max()) > max_pairs:
-            raise ValueError(f"periodic k-NN: a query has {int(hcounts.max())} points within its open-box k-th "
-                             f"distance, more than max_pairs = {max_pairs}; raise max_pairs")
+    if slices:
         err = torch.zeros(1, dtype=torch.int32, device=index.device)
-        a = 0
-        while a < m:
-            # the longest run of rows from a within max_pairs pairs (at least one: checked above)
-            b = int(torch.searchsorted(hcum, hcum[a] + max_pairs, right=True)) - 1
-            b = max(a + 1, min(b, m))
-            offsets = (cum[a:b + 1] - cum[a]).contiguous()
-            K.pknn_rows_gpu(tree, index.perm, qsorted, nq, qlist[a:b].contiguous(), cutq, per, offsets,
-                            int(hcum[b] - hcum[a]), int(hcounts[a:b].max()), qperm, d2, cfg.cut2, cfg.k, out,
-                            out_idx, out_dist, err)
-            a = b
+        for ql, offsets, total, longest in slices:
+            K.pknn_rows_gpu(index.tree(), index.perm, qsorted, nq, ql, cutq, per, offsets, total, longest, qperm, d2,
+                            cfg.cut2, cfg.k, out, out_idx, out_dist, err)
         LAST_PERIODIC_KNN_ERRORS[0] = int(err.item()) & 0xFFFFFFFF
     if stats is not None:
         for nm, v in zip(_RADIUS_PERIODIC_STATS, raw.cpu().tolist()):
             stats.counters[nm] = stats.counters.get(nm, 0) + int(v)
-        stats.counters["periodic_flagged"] = stats.counters.get("periodic_flagged", 0) + m
+        stats.counters["periodic_flagged"] = stats.counters.get("periodic_flagged", 0) + qlist.numel()
         stats.counters["periodic_pairs"] = stats.counters.get("periodic_pairs", 0) + pairs
     if LAST_PERIODIC_KNN_ERRORS[0]:
         raise NativeError(f"periodic k-NN: {LAST_PERIODIC_KNN_ERRORS[0]} rows were not filled to their count or held "
@@ -2138,7 +2153,7 @@ def cluster_points(points: torch.Tensor, eps: float, min_pts: int = 1, squared: 
 # ------------------------------------------------------------------ minimum spanning tree
 # the device error word of the last mst_edges / device mst_labels run (tests: always 0)
 LAST_MST_ERRORS = [0]
-_MST_STATS = ("mst_evals", "mst_nodes", "mst_buckets", None, "mst_cas_retries")
+_MST_STATS = ("mst_evals", "mst_nodes", "mst_buckets", "mst_images", "mst_cas_retries")
 
 
 def _mst_core(what: str, core_d2, n: int, device: torch.device) -> torch.Tensor | None:
@@ -2157,18 +2172,67 @@ def _mst_core(what: str, core_d2, n: int, device: torch.device) -> torch.Tensor 
     return core_d2.contiguous() + 0.0
 
 
-def mst_core_d2(index: LocalIndex, k: int) -> torch.Tensor:
+def _periodic_kth_d2(index: LocalIndex, per: tuple, k: int, max_pairs: int = 1 << 28) -> torch.Tensor:
+    """The squared periodic k-th-neighbour distance of every point of a GPU index (n >= 1), in
+    sorted positions: the flag, count and fill passes of the periodic k-NN (knn_periodic.hip) over
+    the index's own points, with the k-th smallest pd2 of a flagged row taken by its bits, so no
+    value passes through a square root. An unflagged point keeps its open-box value."""
+    n, dev = index.n, index.device
+    cfg = KnnConfig(k=int(k))
+    LAST_PERIODIC_KNN_ERRORS[0] = 0
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+    qsorted, qperm, d2 = _foreign_kth(index, index.pts[:n].contiguous(), cfg, None, out, want_d2=True)
+    res = torch.empty(n, dtype=torch.float32, device=dev)
+    res[qperm.long()] = d2
+    if k > n or all(math.isinf(v) for v in per):  # (k > n: the cutoff under any distance)
+        return res
+    cutq, _, _, slices = _flagged_slices("mst_core_d2", index, per, cfg, qsorted, d2, max_pairs)
+    if not slices:
+        return res
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    short = torch.zeros((), dtype=torch.bool, device=dev)
+    for ql, offsets, total, _ in slices:
+        _, pd2 = K.pknn_fill_gpu(index.tree(), index.perm, qsorted, n, ql, cutq, per, offsets, total, err)
+        # ascending by (row, bits of pd2): the k-th of every row stands at its offset + k - 1
+        lens = offsets[1:] - offsets[:-1]
+        row = torch.repeat_interleave(torch.arange(ql.numel(), device=dev), lens)
+        key = torch.sort((row << 32) | pd2.view(torch.int32).long()).values
+        have = lens >= k
+        short |= (~have & (d2[ql.long()] < cfg.cut2)).any()
+        take = (offsets[:-1] + (k - 1))[have]
+        res[qperm[ql.long()[have]].long()] = (key[take] & 0xFFFFFFFF).int().view(torch.float32)
+    LAST_PERIODIC_KNN_ERRORS[0] = (int(err.item()) & 0xFFFFFFFF) + int(short.item())
+    if LAST_PERIODIC_KNN_ERRORS[0]:
+        raise NativeError("mst_core_d2: a periodic row was not filled to its count or held fewer than k points "
+                          "within the open-box k-th distance (a bug: that distance bounds the periodic one)")
+    return res
+
+
+def mst_core_d2(index: LocalIndex, k: int, period=None) -> torch.Tensor:
     """Core distances for mst_edges: float32 [n] in the order of the indexed array's rows, the
     squared distance from every point to its k-th nearest neighbour (itself counted: query's own
     value, 1 <= k <= the number of finite points), and 0 for a point with a NaN or infinite
-    coordinate, which is no vertex."""
+    coordinate, which is no vertex. period (cluster_labels' values): the k-th smallest periodic
+    squared distance pd2 by its bits, taken before any square root, for mst_edges(..., period=)."""
     if isinstance(k, bool) or int(k) != k or k < 1:
         raise ValueError(f"mst_core_d2: k must be an integer >= 1 (got {k})")
+    per = None
+    if period is not None:
+        per = K.check_period("mst_core_d2", period)
+        if index.qrot is not None or index.line:
+            raise ValueError("mst_core_d2: a period is not supported for an index built in a rotated frame or "
+                             "sorted by line keys")
     n = index.n
     out = torch.zeros(n, dtype=torch.float32, device=index.device)
     if n == 0:
         return out
-    d2 = query(index, KnnConfig(k=int(k)), radius_hint(index.box, n, int(k)))
+    if per is None:
+        d2 = query(index, KnnConfig(k=int(k)), radius_hint(index.box, n, int(k)))
+    elif not K.is_gpu(index.pts):
+        KERNELS_USED.add("cpu")
+        d2 = K.kth_periodic_cpu(index.pts[:n], index.pts[:n], int(k), KnnConfig(k=int(k)).cut2, per)
+    else:
+        d2 = _periodic_kth_d2(index, per, int(k))
     d2 = torch.where(torch.isfinite(index.pts[:n]).all(dim=1), d2[:n], torch.zeros_like(d2[:n]))
     out[index.perm[:n].long()] = d2
     return out
@@ -2179,7 +2243,7 @@ def _empty_mst(device: torch.device) -> tuple[torch.Tensor, torch.Tensor]:
 
 
 def mst_edges(index: LocalIndex, core_d2: torch.Tensor | None = None,
-              stats: KnnStats | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+              stats: KnnStats | None = None, period=None) -> tuple[torch.Tensor, torch.Tensor]:
     """The Euclidean minimum spanning tree of the points of `index`: (rows int32 [m, 2], d2
     float32 [m]), the single-linkage hierarchy at every linking length at once.
 
@@ -2204,20 +2268,39 @@ def mst_edges(index: LocalIndex, core_d2: torch.Tensor | None = None,
     does an index built in a rotated frame or keyed along a line. A round beyond ceil(log2(n)),
     a final edge count other than m or a non-zero error word raise NativeError (a bug, no
     fallback). `stats` receives mst_rounds, mst_evals / _nodes / _buckets / _cas_retries and
-    mst_components, the component count before every round. There is no period."""
+    mst_components, the component count before every round.
+
+    period: None, one value L or (Lx, Ly, Lz), each > 0, inf = open axis (cluster_labels' values;
+    anything else raises ValueError before any kernel runs). The weight of {a, b} is then pd2(a,
+    b), the float32 minimum-image squared distance of radius_counts (per axis d = q - p, h = 0.5f
+    L, d > h: d - L, d < -h: d + L, then the canonical dist2; symmetric in its bits), or with
+    core_d2 max(pd2, core_d2[a], core_d2[b]) (mst_core_d2(index, k, period=) gives the periodic
+    core distances). Key, vertices, m and order are as above, and the result equals
+    K.mst_periodic_cpu bit for bit. There is no bound on the length of an edge and no requirement
+    that the coordinates lie inside one period: every pair has exactly one wrap vector in {-1, 0,
+    +1}^3 by that definition. It is the physical distance of the periodic box only for
+    coordinates inside one period: wrap_points brings them there. For a tree built with period=P
+    and without core_d2, mst_labels(rows, d2, n, eps) equals cluster_labels(index, eps, 1,
+    period=P)[0] bit for bit at every eps that cluster_labels accepts under P; above that bound
+    mst_labels still works. period=(inf, inf, inf) takes the periodic path and equals the open
+    result bit for bit. `stats` additionally receives mst_images, the image walks beyond image 0
+    summed over waves and rounds (0 in the open box)."""
     if index.qrot is not None or index.line:
         raise ValueError("mst_edges: an index built in a rotated frame or keyed along a line cannot serve "
                          "(build_index(points) without a frame)")
+    per = None if period is None else K.check_period("mst_edges", period)
     n, dev = index.n, index.device
     core = _mst_core("mst_edges", core_d2, n, dev)
     if n == 0:
         return _empty_mst(dev)
     if not K.is_gpu(index.pts):
         KERNELS_USED.add("cpu")
-        return K.mst_cpu(_input_order(index), core)
+        return K.mst_cpu(_input_order(index), core) if per is None else \
+            K.mst_periodic_cpu(_input_order(index), per, core)
     perm = index.perm[:n]
     raw = torch.zeros(K.MST_STATS, dtype=torch.int64, device=dev) if stats is not None else None
-    state = K.MstState(index.tree(), index.perm, core[perm.long()].contiguous() if core is not None else None, raw)
+    state = K.MstState(index.tree(), index.perm, core[perm.long()].contiguous() if core is not None else None, raw,
+                       period=per)
     KERNELS_USED.add("mst")
     n_finite = int(torch.isfinite(index.pts[:n]).all(dim=1).sum().item())
     want = max(n_finite - 1, 0)
@@ -2242,8 +2325,7 @@ def mst_edges(index: LocalIndex, core_d2: torch.Tensor | None = None,
         raise NativeError(f"mst_edges: {done} edges for {n_finite} finite points (a bug)")
     if stats is not None:
         for nm, v in zip(_MST_STATS, raw.cpu().tolist()):
-            if nm:
-                stats.counters[nm] = stats.counters.get(nm, 0) + int(v)
+            stats.counters[nm] = stats.counters.get(nm, 0) + int(v)
         stats.counters["mst_rounds"] = rounds
         stats.counters["mst_components"] = comps
     rows, d2 = state.rows[:want], state.d2[:want]
@@ -2255,15 +2337,17 @@ def mst_edges(index: LocalIndex, core_d2: torch.Tensor | None = None,
 
 
 def mst_points(points: torch.Tensor, core_d2: torch.Tensor | None = None,
-               stats: KnnStats | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+               stats: KnnStats | None = None, period=None) -> tuple[torch.Tensor, torch.Tensor]:
     """mst_edges over an index built once from `points` (float32 [n, 3]), in the points' own
-    frame."""
+    frame. period: see mst_edges."""
     if points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32:
         raise ValueError("mst_points: points must be a float32 [n, 3] tensor")
+    if period is not None:  # (before an index is built)
+        K.check_period("mst_points", period)
     if points.shape[0] == 0:  # nothing to index
         _mst_core("mst_points", core_d2, 0, points.device)
         return _empty_mst(points.device)
-    return mst_edges(build_index(points), core_d2, stats=stats)
+    return mst_edges(build_index(points), core_d2, stats=stats, period=period)
 
 
 def mst_labels(rows: torch.Tensor, d2: torch.Tensor, n: int, eps: float, squared: bool = False) -> torch.Tensor:

@@ -925,14 +925,15 @@ def mst_labels_cpu(rows: torch.Tensor, d2: torch.Tensor, n: int, cut2: float) ->
     return labels
 
 
-MST_STATS = 5  # mst.hip: distance evaluations, nodes popped, buckets scanned, unused, CAS retries
+MST_STATS = 5  # mst.hip: distance evaluations, nodes popped, buckets scanned, image walks (periodic), CAS retries
 
 
 class MstState:
     """The device buffers of the Boruvka rounds over one tree (mst.hip): O(n)."""
 
     def __init__(self, tree: tuple, perm: torch.Tensor, core_sorted: torch.Tensor | None,
-                 stats: torch.Tensor | None = None):
+                 stats: torch.Tensor | None = None, period: tuple[float, float, float] | None = None):
+        """period: check_period's values (the periodic rounds), None: the open box."""
         pts, nodes, qnodes, n, depth = tree
         dev = pts.device
         if perm.dtype != torch.int32 or perm.numel() < n or not perm.is_contiguous() or perm.device != dev:
@@ -944,6 +945,7 @@ class MstState:
             raise ValueError(f"mst_gpu: stats int64 [{MST_STATS}] on the tree's device")
         self.tv = TreeView(_ptr(pts), _ptr(nodes), _ptr(qnodes), n, depth, 0)
         self.keep = (pts, nodes, qnodes, perm, core_sorted, stats)  # (the view holds raw pointers)
+        self.period = None if period is None else _period_c(period)
         self.n = n
         self.parent = torch.arange(n, dtype=torch.int32, device=dev)
         self.comp = torch.empty(n, dtype=torch.int32, device=dev)
@@ -960,10 +962,14 @@ class MstState:
     def round(self) -> None:
         """One Boruvka round on the current stream (no host read)."""
         pts, _, _, perm, core, stats = self.keep
-        check(_native.hip().lsk_hip_mst_round(
-            C.byref(self.tv), _ptr(perm), _ptr(core), _ptr(self.parent), _ptr(self.comp), _ptr(self.ncomp),
-            _ptr(self.best), _ptr(self.best_pos), _ptr(self.cmin), _ptr(self.chi), _ptr(self.rows), _ptr(self.d2),
-            _ptr(self.count), _ptr(self.err), _ptr(stats), _stream(pts)), "mst_round")
+        tail = (_ptr(self.parent), _ptr(self.comp), _ptr(self.ncomp), _ptr(self.best), _ptr(self.best_pos),
+                _ptr(self.cmin), _ptr(self.chi), _ptr(self.rows), _ptr(self.d2), _ptr(self.count), _ptr(self.err),
+                _ptr(stats), _stream(pts))
+        if self.period is None:
+            check(_native.hip().lsk_hip_mst_round(C.byref(self.tv), _ptr(perm), _ptr(core), *tail), "mst_round")
+        else:
+            check(_native.hip().lsk_hip_mst_periodic_round(C.byref(self.tv), _ptr(perm), _ptr(core), self.period,
+                                                           *tail), "mst_periodic_round")
 
 
 def mst_labels_gpu(rows: torch.Tensor, d2: torch.Tensor, n: int, cut2: float) -> tuple[torch.Tensor, torch.Tensor]:
@@ -1374,6 +1380,24 @@ def knn_periodic_cpu(points: torch.Tensor, queries: torch.Tensor, k: int, cut2: 
     return idx, d2
 
 
+def mst_periodic_cpu(points: torch.Tensor, period, core_d2: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """CPU oracle of the periodic minimum spanning tree: mst_cpu with dist2 replaced by the
+    periodic squared distance of radius_periodic_count_cpu (symmetric in its bits), whatever the
+    length of an edge and wherever the coordinates lie."""
+    per = check_period("mst_periodic_cpu", period)
+    pts = points.contiguous().float().cpu()
+    n = pts.shape[0]
+    core = None
+    if core_d2 is not None:
+        core = core_d2.contiguous().float().cpu()
+        if core.dim() != 1 or core.shape[0] != n or not bool((torch.isfinite(core) & (core >= 0)).all()):
+            raise ValueError("mst_periodic_cpu: core_d2 must hold n finite entries >= 0")
+    rows = torch.empty((max(n - 1, 0), 2), dtype=torch.int32)
+    d2 = torch.empty(max(n - 1, 0), dtype=torch.float32)
+    m = int(_native.host().lsk_cpu_mst_periodic(_ptr(pts), n, _ptr(core), _period_c(per), _ptr(rows), _ptr(d2)))
+    return rows[:m].contiguous(), d2[:m].contiguous()
+
+
 def _pknn_view(what: str, tree: tuple, qsorted: torch.Tensor, nq: int, **arrays) -> TreeView:
     """The view of `tree` for the periodic k-NN passes; arrays: name = (tensor, dtype, least size)."""
     pts, nodes, qnodes, n, depth = tree
@@ -1413,6 +1437,27 @@ def pknn_count_gpu(tree: tuple, qsorted: torch.Tensor, nq: int, qlist: torch.Ten
     return counts
 
 
+def pknn_fill_gpu(tree: tuple, perm: torch.Tensor, qsorted: torch.Tensor, nq: int, qlist: torch.Tensor,
+                  cutq: torch.Tensor, period: tuple[float, float, float], offsets: torch.Tensor, total: int,
+                  err: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """The fill pass of pknn_rows_gpu, also on its own: (idx int32 [total], pd2 float32 [total]),
+    the rows `offsets` in walk order with the periodic squared distances as the walk computed
+    them (no sort, no square root)."""
+    m = qlist.numel()
+    tv = _pknn_view("pknn_fill_gpu", tree, qsorted, nq, qlist=(qlist, torch.int32, m), cutq=(cutq, torch.float32, nq),
+                    perm=(perm, torch.int32, tree[3]), offsets=(offsets, torch.int64, m + 1),
+                    err=(err, torch.int32, 1))
+    if offsets.numel() != m + 1:
+        raise ValueError("pknn_fill_gpu: offsets must be [m + 1]")
+    dev = tree[0].device
+    idx = torch.empty(total, dtype=torch.int32, device=dev)
+    pd2 = torch.empty(total, dtype=torch.float32, device=dev)
+    check(_native.hip().lsk_hip_pknn_fill(C.byref(tv), _ptr(perm), _ptr(qsorted), _ptr(qlist), int(m), _ptr(cutq),
+                                          _period_c(period), _ptr(offsets), _ptr(idx), _ptr(pd2), _ptr(err),
+                                          _stream(tree[0])), "pknn_fill")
+    return idx, pd2
+
+
 def pknn_rows_gpu(tree: tuple, perm: torch.Tensor, qsorted: torch.Tensor, nq: int, qlist: torch.Tensor,
                   cutq: torch.Tensor, period: tuple[float, float, float], offsets: torch.Tensor, total: int,
                   longest: int, qperm: torch.Tensor, d2: torch.Tensor, cut2: float, k: int, out: torch.Tensor,
@@ -1431,12 +1476,8 @@ def pknn_rows_gpu(tree: tuple, perm: torch.Tensor, qsorted: torch.Tensor, nq: in
     tv = _pknn_view("pknn_rows_gpu", tree, qsorted, nq, **arrays)
     if offsets.numel() != m + 1 or k < 1:
         raise ValueError("pknn_rows_gpu: offsets must be [m + 1] and k >= 1")
-    dev = tree[0].device
     lib, st = _native.hip(), _stream(tree[0])
-    idx = torch.empty(total, dtype=torch.int32, device=dev)
-    dist = torch.empty(total, dtype=torch.float32, device=dev)
-    check(lib.lsk_hip_pknn_fill(C.byref(tv), _ptr(perm), _ptr(qsorted), _ptr(qlist), int(m), _ptr(cutq),
-                                _period_c(period), _ptr(offsets), _ptr(idx), _ptr(dist), _ptr(err), st), "pknn_fill")
+    idx, dist = pknn_fill_gpu(tree, perm, qsorted, nq, qlist, cutq, period, offsets, total, err)
     check(lib.lsk_hip_radius_sort(_ptr(offsets), int(m), int(total), int(longest), _ptr(idx), _ptr(dist), 1, st),
           "radius_sort")
     check(lib.lsk_hip_pknn_take(_ptr(qlist), int(m), _ptr(offsets), _ptr(idx), _ptr(dist), _ptr(qperm), _ptr(d2),

@@ -3,7 +3,7 @@
 and for the first Boruvka round alone.
 
     python scripts/mst_bench.py [--data uniform|clustered] [--points N] [--steps 5] [--warmup 2]
-                                [--f 0.9] [--core-k K]
+                                [--f 0.9] [--core-k K] [--period L]
 
 On one index, device-synchronised host clock, medians over the steps after the warm-up steps,
 the cases timed alternately step by step:
@@ -16,7 +16,9 @@ the cases timed alternately step by step:
 Defaults: 1e7 uniform points, 2e7 clustered (100 Gaussian blobs, sigma 0.01). Prints one JSON line
 with the times, the rounds, the component counts and the distance evaluations per point and
 round. The tree is checked on the spot: n - 1 edges, and mst_labels at eps equal to the labels of
-cluster_labels.
+cluster_labels. --period L: the tree, the core distances and the labels under the period L on every
+axis (the generated points lie in the unit box: --period 1 wraps every face); the record then
+also holds the period and the image walks beyond image 0 per wave and round.
 """
 from __future__ import annotations
 
@@ -49,6 +51,7 @@ def main() -> int:
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--f", type=float, default=0.9)
     ap.add_argument("--core-k", type=int, default=0)
+    ap.add_argument("--period", type=float, default=None, help="periodic box of this period on every axis")
     ap.add_argument("--mst-only", action="store_true", help="time nothing but the tree")
     a = ap.parse_args()
     import torch
@@ -62,11 +65,12 @@ def main() -> int:
     extent = float((p.max(0).values - p.min(0).values).max())
     eps = a.f * extent * n ** (-1.0 / 3.0)
     index = E.build_index(p, grid=a.core_k > 0)
-    core = E.mst_core_d2(index, a.core_k) if a.core_k else None
+    per = {} if a.period is None else {"period": a.period}  # (open box: the calls of the open path, unchanged)
+    core = E.mst_core_d2(index, a.core_k, **per) if a.core_k else None
     out = {}
-    cases = {"mst": lambda: out.__setitem__("m", E.mst_edges(index, core))}
+    cases = {"mst": lambda: out.__setitem__("m", E.mst_edges(index, core, **per))}
     if not a.mst_only:
-        cases["cluster"] = lambda: out.__setitem__("l", E.cluster_labels(index, eps, 1))
+        cases["cluster"] = lambda: out.__setitem__("l", E.cluster_labels(index, eps, 1, **per))
         cases["knn2"] = lambda: out.__setitem__("k", E.knn_neighbors(p, 2))
     times = {name: [] for name in cases}
     for step in range(a.warmup + a.steps):
@@ -80,11 +84,11 @@ def main() -> int:
                 times[name].append(time.perf_counter() - t0)
     med = {name: statistics.median(ts) for name, ts in times.items()}
     stats = E.KnnStats()
-    rows, d2 = E.mst_edges(index, core, stats=stats)
+    rows, d2 = E.mst_edges(index, core, stats=stats, **per)
     c = stats.counters
     ok = rows.shape[0] == n - 1
     if core is None:
-        ok = ok and torch.equal(E.mst_labels(rows, d2, n, eps), E.cluster_labels(index, eps, 1)[0])
+        ok = ok and torch.equal(E.mst_labels(rows, d2, n, eps), E.cluster_labels(index, eps, 1, **per)[0])
     rec = {"data": a.data, "points": n, "core_k": a.core_k, "steps": a.steps, "warmup": a.warmup,
            "mst_s": med["mst"], "mst_Mpoints_per_s": n / med["mst"] / 1e6,
            "rounds": c["mst_rounds"], "components": c["mst_components"],
@@ -96,6 +100,10 @@ def main() -> int:
            "mst_over_knn2": med["mst"] / med["knn2"] if "knn2" in med else None,
            "spread": {name: [min(ts), max(ts)] for name, ts in times.items()},
            "checked": bool(ok)}
+    if a.period is not None:
+        waves = (n + 63) // 64
+        rec.update(period=a.period, mst_images=c["mst_images"],
+                   images_per_wave_per_round=c["mst_images"] / waves / max(c["mst_rounds"], 1))
     print(json.dumps(rec), flush=True)
     return 0 if ok else 1
 
