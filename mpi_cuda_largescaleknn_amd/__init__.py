@@ -47,4 +47,6 @@ from .models.knn_engine import (KnnConfig, build_index, cluster_labels, cluster_
                                 pair_counts, pair_query_counts, pair_self_counts, PointWeights,
                                 prepare_point_weights, fixed_point_weights, weighted_profile, weighted_query_profile,
                                 weighted_self_profile, weighted_pair_sums, weighted_pair_query_sums,
-                                weighted_pair_self_sums, mst_edges, mst_points, mst_labels)
+                                weighted_pair_self_sums, mst_edges, mst_points, mst_labels,
+                                pair_counts_rppi, pair_query_counts_rppi, pair_self_counts_rppi, pair_counts_smu,
+                                pair_query_counts_smu, pair_self_counts_smu, shell_counts_2d)

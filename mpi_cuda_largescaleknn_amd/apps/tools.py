@@ -22,6 +22,10 @@
            [--query-weights WQ.i64] [--pairs-only] ...
            -> hipKNN_radius --profile --weights' PREFIX.wprofile and PREFIX.wpairs against the oracle, on
               the same sampling rules
+    python -m mpi_cuda_largescaleknn_amd.apps.tools pcheck in.float3 q.float3 PREFIX (--rp .. --pi .. | --s .. --mu ..)
+           [--los x|y|z] [--squared] [--period L | Lx,Ly,Lz]
+           -> hipKNN_pairs' PREFIX.pairs2d against the brute-force oracle, every cell (at most 65536
+              queries: the oracle visits every pair)
     python -m mpi_cuda_largescaleknn_amd.apps.tools fixweights in.float out.i64 [--bits N] [--terms T]
            -> float32 masses as exact fixed-point int64 weights
               (knn_engine.fixed_point_weights); prints the exponent s: physical sum = result * 2^s
@@ -189,6 +193,32 @@ def _rcheck_profile(a, pts, qry) -> int:
     for b in off[:10].tolist():
         print(f"PAIRS {b} = {int(pairs[b])} (column sum {int(sums[b])})")
     return 0 if bad + off.numel() == 0 else 1
+
+
+def pcheck(a) -> int:
+    """PREFIX.pairs2d of hipKNN_pairs against the oracle, every cell."""
+    from ..models.knn_engine import _pairs2d_cutoffs
+    try:
+        a2, b2, los, per = _pairs2d_cutoffs("pcheck", a.mode, a.first, a.second, a.los, a.squared, a.period)
+    except ValueError as e:
+        print(e)
+        return 1
+    pts, qry = io.read_points(a.inp), io.read_points(a.queries)
+    if qry.shape[0] > CCHECK_MAX:
+        print(f"pcheck: {qry.shape[0]} queries, more than {CCHECK_MAX}: the oracle visits every pair; check a "
+              "smaller set")
+        return 1
+    got = io.read_array(a.prefix + ".pairs2d", torch.int64)
+    if got.shape[0] != a2.shape[0] * b2.shape[0]:
+        print(f"size mismatch: {got.shape[0]} cells for {a2.shape[0]} x {b2.shape[0]} edges")
+        return 1
+    got = got.view(a2.shape[0], b2.shape[0])
+    ref = K.pair_counts_2d_cpu(pts, qry, a2, b2, a.mode, los, per)
+    wrong = (got != ref).nonzero()
+    print(f"checked {ref.numel()} cells: {wrong.shape[0]} mismatches")
+    for i, j in wrong[:10].tolist():
+        print(f"PAIRS2D [{i}][{j}] = {int(got[i, j])} (oracle {int(ref[i, j])})")
+    return 0 if wrong.shape[0] == 0 else 1
 
 
 def _rcheck_weighted(a, pts, qry) -> int:
@@ -486,6 +516,13 @@ def main(argv=None) -> int:
                    help="rows compared (default 1000; --profile: every row of up to 65536)")
     p.add_argument("--counts-only", action="store_true")
     p.add_argument("--unsorted", action="store_true", help="rows written with --unsorted: compared as sets")
+    p = sub.add_parser("pcheck")
+    p.add_argument("inp")
+    p.add_argument("queries")
+    p.add_argument("prefix", help="the -o PREFIX of hipKNN_pairs")
+    from .pairs import add_pairs_options, pairs_mode
+    add_pairs_options(p)
+    pcheck_parser = p
     p = sub.add_parser("fixweights")
     p.add_argument("inp", help="headerless float32 file of weights (masses)")
     p.add_argument("out", help="headerless int64 file")
@@ -519,7 +556,9 @@ def main(argv=None) -> int:
     a = ap.parse_args(argv)
     if a.cmd == "wrap" and a.period is None:
         ap.error("wrap: --period is required")
-    return {"gen": gen, "split": split, "check": check, "rcheck": rcheck, "ccheck": ccheck, "mcheck": mcheck, "wrap": wrap,
+    if a.cmd == "pcheck":
+        pairs_mode(pcheck_parser, a)
+    return {"pcheck": pcheck, "gen": gen, "split": split, "check": check, "rcheck": rcheck, "ccheck": ccheck, "mcheck": mcheck, "wrap": wrap,
             "cat": cat,
             "cmp": cmp, "fixweights": fixweights}[a.cmd](a)
 

@@ -530,6 +530,53 @@ extern "C" void lsk_cpu_weighted_profile(const float *pts, int64_t n, const floa
   });
 }
 
+// Anisotropic pair counts along the line-of-sight axis `los` (pair_counts_2d.hip states the
+// contract). Per pair the float32 differences q - p (period: their minimum image) give par2 = dl
+// * dl of the line-of-sight axis, perp2 = fmaf(db, db, da * da) of the other two in ascending axis
+// order, and the canonical d2. mode 0, (rp, pi): the pair's cell is i0 = #{i : !(perp2 < a2[i])},
+// j0 = #{j : !(par2 < b2[j])}; mode 1, (s, mu): i0 = #{i : !(d2 < a2[i])}, j0 = #{j : !(par2 <
+// b2[j] * d2)} (one float32 product). A pair with i0 == na or j0 == nb is dropped. Every thread
+// counts differential cells of its own; out [na, nb] is the 2-D prefix sum of their total.
+extern "C" void lsk_cpu_pair_counts_2d(const float *pts, int64_t n, const float *qry, int64_t nq, const float *a2,
+                                       int32_t na, const float *b2, int32_t nb, int mode, int los,
+                                       const float *period, int64_t *out, int nthreads) {
+  const vec3f *P = (const vec3f *)pts;
+  const vec3f *Q = (const vec3f *)qry;
+  if (na <= 0 || nb <= 0) return;
+  const size_t cells = (size_t)na * (size_t)nb;
+  std::vector<uint64_t> total(cells, 0);
+  std::mutex mu;
+  parallel_for(nq, nthreads, [&](int64_t b, int64_t e) {
+    std::vector<uint64_t> cell(cells, 0);
+    for (int64_t qi = b; qi < e; qi++) {
+      for (int64_t i = 0; i < n; i++) {
+        float d[3] = {Q[qi].x - P[i].x, Q[qi].y - P[i].y, Q[qi].z - P[i].z};
+        if (period)
+          for (int a = 0; a < 3; a++) d[a] = wrap_diff(d[a], period[a]);
+        const float dl = d[los], da = d[los == 0 ? 1 : 0], db = d[los == 2 ? 1 : 2];
+        const float par2 = dl * dl;
+        const float va = mode == 0 ? fmaf(db, db, da * da) : lsk::dist2(d[0], d[1], d[2]);
+        const float *ia = std::partition_point(a2, a2 + na, [va](float c) { return !(va < c); });
+        if (ia == a2 + na) continue;
+        const float *jb = mode == 0
+                              ? std::partition_point(b2, b2 + nb, [par2](float c) { return !(par2 < c); })
+                              : std::partition_point(b2, b2 + nb, [par2, va](float c) { return !(par2 < c * va); });
+        if (jb == b2 + nb) continue;
+        cell[(size_t)(ia - a2) * (size_t)nb + (size_t)(jb - b2)]++;
+      }
+    }
+    std::lock_guard<std::mutex> lk(mu);
+    for (size_t c = 0; c < cells; c++) total[c] += cell[c];
+  });
+  for (int32_t i = 0; i < na; i++) {
+    uint64_t run = 0;
+    for (int32_t j = 0; j < nb; j++) {
+      run += total[(size_t)i * nb + j];
+      out[(size_t)i * nb + j] = (int64_t)(run + (i ? (uint64_t)out[(size_t)(i - 1) * nb + j] : 0));
+    }
+  }
+}
+
 // lsk_cpu_kth_brute under a period: the k-th smallest pdist2 among those < cut2, else cut2.
 extern "C" void lsk_cpu_kth_periodic(const float *pts, int64_t n, const float *qry, int64_t nq, int k, float cut2,
                                      const float *period, float *out_d2, int nthreads) {

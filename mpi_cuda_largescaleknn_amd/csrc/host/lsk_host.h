@@ -141,6 +141,14 @@ void lsk_cpu_radius_profile(const float *pts, int64_t n, const float *qry, int64
 // Sums wrap in 64 bits: exact when sum |w| < 2^63.
 void lsk_cpu_weighted_profile(const float *pts, int64_t n, const float *qry, int64_t nq, const float *cut2s,
                               int32_t nb, const float *period, const int64_t *w, int64_t *out, int nthreads);
+// Anisotropic pair counts by brute force over all pairs: out (int64 [na, nb]) is cumulative on both
+// axes. los in {0, 1, 2} picks the line-of-sight difference dl of q - p (period: its minimum
+// image); par2 = dl * dl, perp2 = fmaf(db, db, da * da) of the other two axes in ascending order.
+// mode 0: out[i, j] = #{pairs : perp2 < a2[i] and par2 < b2[j]}; mode 1: #{pairs : d2 < a2[i] and
+// par2 < b2[j] * d2}. a2 / b2: na, nb >= 1 ascending values >= 0, +inf allowed, no NaN.
+void lsk_cpu_pair_counts_2d(const float *pts, int64_t n, const float *qry, int64_t nq, const float *a2, int32_t na,
+                            const float *b2, int32_t nb, int mode, int los, const float *period, int64_t *out,
+                            int nthreads);
 // lsk_cpu_kth_brute / lsk_cpu_knn_brute under a period: brute force over all points with the
 // periodic squared distance above, the same selection (k-th smallest by bits among those <
 // cut2, else cut2) and the same tie rule (ascending (d² bits, row); unfilled: -1 / cut2).

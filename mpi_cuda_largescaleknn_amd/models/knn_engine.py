@@ -1703,6 +1703,181 @@ def pair_self_counts(points: torch.Tensor, radii, squared: bool = False, period=
     return pair_query_counts(points, points, radii, squared=squared, period=period, stats=stats)
 
 
+# ---- anisotropic pair counts: DD(rp, pi) and DD(s, mu) along a box axis (pair_counts_2d.hip)
+_LOS = {"x": 0, "y": 1, "z": 2}
+
+
+def _edge_values(what: str, name: str, edges) -> list:
+    """The numbers of one list of bin edges (a sequence or a float32 / float64 CPU tensor [B], 1 <=
+    B <= 2048), each >= 0 and not NaN, ascending; nothing on a device is read."""
+    if isinstance(edges, torch.Tensor):
+        if edges.device.type != "cpu" or edges.dtype not in (torch.float32, torch.float64) or edges.dim() != 1:
+            raise ValueError(f"{what}: {name} must be a sequence or a float32 / float64 CPU tensor [B] "
+                             f"(got {edges.dtype} {tuple(edges.shape)} on {edges.device})")
+        vals = edges.tolist()
+    else:
+        try:
+            vals = [float(r) for r in edges]
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: {name} must be a sequence of numbers or a CPU tensor") from None
+    if not 1 <= len(vals) <= K.PAIRS2D_MAX_EDGES:
+        raise ValueError(f"{what}: {name} must hold 1 .. {K.PAIRS2D_MAX_EDGES} values (got {len(vals)})")
+    if any(math.isnan(v) or v < 0.0 for v in vals):
+        raise ValueError(f"{what}: every value of {name} must be >= 0 (got {vals})")
+    if any(b < a for a, b in zip(vals, vals[1:])):
+        raise ValueError(f"{what}: {name} must ascend (got {vals})")
+    return vals
+
+
+def _pairs2d_cutoffs(what: str, mode: str, first, second, los, squared: bool, period) -> tuple:
+    """The checked arguments of an anisotropic pair count: (a2, b2 float32 CPU tensors, los in {0,
+    1, 2}, period values or None). mode 'rppi': first = rp, second = pi; 'smu': first = s, second
+    = mu (always plain mu, squared by cut2_of). Under a period a line-of-sight radius (pi, s) may
+    not exceed period_radius_bound of the line-of-sight axis and a perpendicular radius (rp, s)
+    not that of the two other axes. ValueError otherwise; nothing on a device is read."""
+    if isinstance(los, str):
+        los = _LOS.get(los.lower(), -1)
+    if isinstance(los, bool) or not isinstance(los, int) or los not in (0, 1, 2):
+        raise ValueError(f"{what}: los must be 0, 1, 2 or 'x', 'y', 'z'")
+    n1, n2 = ("rp", "pi") if mode == "rppi" else ("s", "mu")
+    v1, v2 = _edge_values(what, n1, first), _edge_values(what, n2, second)
+    if len(v1) * len(v2) > K.PAIRS2D_MAX_CELLS:
+        raise ValueError(f"{what}: {len(v1)} x {len(v2)} cells exceed {K.PAIRS2D_MAX_CELLS}")
+    per = None if period is None else K.check_period(what, period)
+    if per is not None:
+        along = period_radius_bound((per[los],), squared)
+        across = period_radius_bound(tuple(per[a] for a in range(3) if a != los), squared)
+        for nm, vals, upper, axis in ((n1, v1, across, "a perpendicular axis"),
+                                      (n1, v1 if mode == "smu" else (), along, "the line-of-sight axis"),
+                                      (n2, v2 if mode == "rppi" else (), along, "the line-of-sight axis")):
+            for r in vals:
+                if float(np.float32(r)) > upper:
+                    raise ValueError(f"{what}: {nm} {r} exceeds half the period of {axis} "
+                                     f"({'squared ' if squared else ''}bound {upper})")
+    a2 = torch.tensor([_radius_cut2(what, r, squared) for r in v1], dtype=torch.float32)
+    b2 = torch.tensor([_radius_cut2(what, r, squared and mode == "rppi") for r in v2], dtype=torch.float32)
+    return a2, b2, los, per
+
+
+def _pairs2d(what: str, mode: str, index: LocalIndex, queries: torch.Tensor, first, second, los, squared: bool,
+             period, stats: KnnStats | None) -> torch.Tensor:
+    a2, b2, los, per = _pairs2d_cutoffs(what, mode, first, second, los, squared, period)
+    if index.qrot is not None or index.line:
+        raise ValueError(f"{what}: an index built in a rotated frame or sorted by line keys is not supported")
+    queries = _check_foreign(what, index, queries)
+    nq, n = queries.shape[0], index.n
+    if nq == 0 or n == 0:
+        return torch.zeros((a2.shape[0], b2.shape[0]), dtype=torch.int64, device=index.device)
+    if not K.is_gpu(index.pts):
+        KERNELS_USED.add("cpu")
+        return K.pair_counts_2d_cpu(index.pts[:n], queries, a2, b2, mode, los, per)
+    qsorted, qperm = prepare_queries(index, queries, locate=False)[:2]
+    names = _RADIUS_STATS if per is None else _RADIUS_PERIODIC_STATS
+    raw = torch.zeros(len(names), dtype=torch.int64, device=index.device) if stats is not None else None
+    out = K.pair_counts_2d_gpu(index.tree(), qsorted, nq, a2, b2, mode, los, qperm, per, stats=raw)
+    KERNELS_USED.add("pair_counts_2d")
+    if stats is not None:
+        for nm, v in zip(names, raw.cpu().tolist()):
+            stats.counters[nm] = stats.counters.get(nm, 0) + int(v)
+    return out
+
+
+def _pairs2d_index(what: str, mode: str, points: torch.Tensor, queries: torch.Tensor, first, second, los,
+                   squared: bool, period) -> tuple:
+    """(index or None, the empty result) of the *_query_* / *_self_* forms (the arguments are
+    checked all the same when there is nothing to index)."""
+    if points.device != queries.device:
+        raise ValueError(f"{what}: points on {points.device}, queries on {queries.device}")
+    if points.shape[0] == 0:
+        a2, b2 = _pairs2d_cutoffs(what, mode, first, second, los, squared, period)[:2]
+        return None, torch.zeros((a2.shape[0], b2.shape[0]), dtype=torch.int64, device=queries.device)
+    return build_index(points), None
+
+
+def pair_counts_rppi(index: LocalIndex, queries: torch.Tensor, rp, pi, los=2, squared: bool = False, period=None,
+                     stats: KnnStats | None = None) -> torch.Tensor:
+    """int64 [Bp, Bl] on the index's device: S[i, j] = the number of pairs (query q, indexed point
+    p) with perp2 < cut2_of(rp[i]) and par2 < cut2_of(pi[j]), strict and cumulative on both axes:
+    the DD / DR counts of the projected two-point function along a box axis, from one walk of the
+    tree and without storing a pair. shell_counts_2d(S) is the binned DD(rp, pi).
+
+    Per pair (dx, dy, dz) are the float32 differences q - p, with `period` their minimum image
+    (as radius_counts; period=(inf, inf, inf) equals the open box bit for bit). los (0, 1, 2 or
+    'x', 'y', 'z') picks the line-of-sight difference dl, the other two in ascending axis order
+    are da, db; par2 = dl * dl, perp2 = fmaf(db, db, da * da). A NaN component passes no test;
+    a query with a NaN or infinite coordinate counts nothing. rp, pi: Python sequences or float32
+    / float64 CPU tensors of 1 .. 2048 values, each >= 0, ascending, duplicates and inf allowed,
+    Bp * Bl <= 65536; squared=True: the squared cutoffs themselves. Under a period every pi may
+    not exceed period_radius_bound of the line-of-sight axis and every rp not that of the shorter
+    finite perpendicular axis. Every argument error raises ValueError before any kernel runs,
+    without a device read; an index built in a rotated frame or sorted by line keys is not
+    supported. `stats` receives the radius_* counters of radius_profile. Grids of more than 2048
+    cells are served in slices of whole rp rows, one walk each. Integer sums: two runs give the
+    same bits. Limit as for radius_profile: whole boxes are counted without visiting their
+    points, which is exact for finite indexed points."""
+    return _pairs2d("pair_counts_rppi", "rppi", index, queries, rp, pi, los, squared, period, stats)
+
+
+def pair_query_counts_rppi(points: torch.Tensor, queries: torch.Tensor, rp, pi, los=2, squared: bool = False,
+                           period=None, stats: KnnStats | None = None) -> torch.Tensor:
+    """pair_counts_rppi over an index built once from `points`, in the points' own frame."""
+    index, empty = _pairs2d_index("pair_query_counts_rppi", "rppi", points, queries, rp, pi, los, squared, period)
+    if index is None:
+        return empty
+    return pair_counts_rppi(index, queries, rp, pi, los=los, squared=squared, period=period, stats=stats)
+
+
+def pair_self_counts_rppi(points: torch.Tensor, rp, pi, los=2, squared: bool = False, period=None,
+                          stats: KnnStats | None = None) -> torch.Tensor:
+    """pair_query_counts_rppi with the points as their own queries: ordered pairs, (p, q) and (q,
+    p) both, and every finite point with itself (perp2 = par2 = 0: in every cell with cutoffs >
+    0), like pair_self_counts."""
+    return pair_query_counts_rppi(points, points, rp, pi, los=los, squared=squared, period=period, stats=stats)
+
+
+def pair_counts_smu(index: LocalIndex, queries: torch.Tensor, s, mu, los=2, squared: bool = False, period=None,
+                    stats: KnnStats | None = None) -> torch.Tensor:
+    """int64 [Bs, Bm] on the index's device: S[i, j] = the number of pairs with d2 < cut2_of(s[i])
+    and par2 < mu2[j] * d2 (one float32 product), mu2[j] = cut2_of(mu[j]): the cumulative counts of
+    DD(s, mu) for the multipoles, mu = |dl| / s being the cosine to the line of sight. d2 is the
+    canonical dist2 of the differences pair_counts_rppi describes, par2 = dl * dl. mu: always
+    plain mu edges, each >= 0, ascending, inf allowed; squared=True applies to s alone. Two
+    consequences of the strict product test: a pair with d2 == 0 (a point with itself, exact
+    copies) counts in no column, and an edge mu = 1 excludes the pairs that lie exactly along the
+    line of sight, which an edge of inf takes in. Under a period every s may exceed neither the
+    bound of the line-of-sight axis nor that of a perpendicular axis. Everything else as for
+    pair_counts_rppi; there is no whole-box acceptance in this mode."""
+    return _pairs2d("pair_counts_smu", "smu", index, queries, s, mu, los, squared, period, stats)
+
+
+def pair_query_counts_smu(points: torch.Tensor, queries: torch.Tensor, s, mu, los=2, squared: bool = False,
+                          period=None, stats: KnnStats | None = None) -> torch.Tensor:
+    """pair_counts_smu over an index built once from `points`, in the points' own frame."""
+    index, empty = _pairs2d_index("pair_query_counts_smu", "smu", points, queries, s, mu, los, squared, period)
+    if index is None:
+        return empty
+    return pair_counts_smu(index, queries, s, mu, los=los, squared=squared, period=period, stats=stats)
+
+
+def pair_self_counts_smu(points: torch.Tensor, s, mu, los=2, squared: bool = False, period=None,
+                         stats: KnnStats | None = None) -> torch.Tensor:
+    """pair_query_counts_smu with the points as their own queries: ordered pairs; a point with
+    itself (d2 == 0) counts nowhere."""
+    return pair_query_counts_smu(points, points, s, mu, los=los, squared=squared, period=period, stats=stats)
+
+
+def shell_counts_2d(S: torch.Tensor) -> torch.Tensor:
+    """The binned counts of a cumulative [B1, B2] array of pair_counts_rppi / pair_counts_smu: its
+    2-D difference, D[i, j] = S[i, j] - S[i - 1, j] - S[i, j - 1] + S[i - 1, j - 1] (terms with
+    an index of -1 are 0): the pairs of cell (i, j) alone."""
+    if S.dim() != 2:
+        raise ValueError(f"shell_counts_2d: a [B1, B2] array is required (got {tuple(S.shape)})")
+    D = S.clone()
+    D[1:, :] -= S[:-1, :]
+    D[:, 1:] -= D[:, :-1].clone()
+    return D
+
+
 # ---- weighted radius profiles: exact sums of int64 point weights within radii (radius_profile.hip)
 def _max_abs(w: torch.Tensor) -> int:
     """max |w| of an int64 tensor as a Python int (one small reduction is read; |-2^63| included)."""

@@ -1268,6 +1268,64 @@ def pair_counts_gpu(tree: tuple, qsorted: torch.Tensor, nq: int, cut2s, out_perm
     return _profile_slices("pair_counts", tree, qsorted, nq, cut2s, out_perm, period, stats, sums=True)
 
 
+# --------------------------------------------------------------------------- anisotropic pair counts
+PAIRS2D_MODES = {"rppi": 0, "smu": 1}
+PAIRS2D_MAX_EDGES = 2048   # pair_counts_2d.hip kMaxEdges: cutoffs per axis
+PAIRS2D_MAX_CELLS = 65536  # pair_counts_2d.hip kMaxGrid: cells of the whole grid
+
+
+def _pairs2d_args(what: str, a2, b2, mode: str, los: int) -> tuple:
+    if mode not in PAIRS2D_MODES:
+        raise ValueError(f"{what}: mode must be 'rppi' or 'smu' (got {mode!r})")
+    if isinstance(los, bool) or los not in (0, 1, 2):
+        raise ValueError(f"{what}: los must be 0, 1 or 2 (got {los!r})")
+    a, b = _profile_cut2s(what, a2), _profile_cut2s(what, b2)
+    if a.shape[0] > PAIRS2D_MAX_EDGES or b.shape[0] > PAIRS2D_MAX_EDGES or \
+            a.shape[0] * b.shape[0] > PAIRS2D_MAX_CELLS:
+        raise ValueError(f"{what}: at most {PAIRS2D_MAX_EDGES} cutoffs per axis and {PAIRS2D_MAX_CELLS} cells "
+                         f"(got {a.shape[0]} x {b.shape[0]})")
+    return a, b
+
+
+def pair_counts_2d_cpu(points: torch.Tensor, queries: torch.Tensor, a2, b2, mode: str, los: int = 2,
+                       period=None) -> torch.Tensor:
+    """CPU oracle (brute force over all pairs) of the anisotropic pair counts: int64 [Ba, Bb],
+    cumulative on both axes. mode 'rppi': S[i, j] = #{pairs : perp2 < a2[i] and par2 < b2[j]};
+    'smu': #{pairs : d2 < a2[i] and par2 < b2[j] * d2}, with par2 = dl * dl of the line-of-sight
+    axis `los` of the float32 differences q - p (period: their minimum image), perp2 = fmaf(db,
+    db, da * da) of the other two. a2 / b2: ascending squared cutoffs (sequences or CPU tensors)."""
+    a, b = _pairs2d_args("pair_counts_2d_cpu", a2, b2, mode, los)
+    per = None if period is None else check_period("pair_counts_2d_cpu", period)
+    pts = points.contiguous().float().cpu()
+    q = queries.contiguous().float().cpu()
+    out = torch.zeros((a.shape[0], b.shape[0]), dtype=torch.int64)
+    _native.host().lsk_cpu_pair_counts_2d(_ptr(pts), pts.shape[0], _ptr(q), q.shape[0], _ptr(a), a.shape[0], _ptr(b),
+                                          b.shape[0], PAIRS2D_MODES[mode], int(los),
+                                          None if per is None else _period_c(per), _ptr(out), _nthreads())
+    return out
+
+
+def pair_counts_2d_gpu(tree: tuple, qsorted: torch.Tensor, nq: int, a2, b2, mode: str, los: int,
+                       out_perm: torch.Tensor, period: tuple[float, float, float] | None = None,
+                       stats: torch.Tensor | None = None) -> torch.Tensor:
+    """The anisotropic pair counts (pair_counts_2d.hip) on the current stream: int64 [Ba, Bb] on the
+    tree's device, what pair_counts_2d_cpu defines, from one walk per slice of 2048 cells; the
+    blocks add their cells to the result, one small kernel makes it cumulative. tree / qsorted /
+    out_perm / period / stats as for pair_counts_gpu."""
+    what = "pair_counts_2d_gpu"
+    a, b = _pairs2d_args(what, a2, b2, mode, los)
+    tv = _walk_view(what, tree, qsorted, nq, out_perm)
+    dev = tree[0].device
+    _profile_stats(what, stats, period, dev)
+    res = torch.empty((a.shape[0], b.shape[0]), dtype=torch.int64, device=dev)
+    adev, bdev = a.to(dev), b.to(dev)
+    check(_native.hip().lsk_hip_pair_counts_2d(C.byref(tv), _ptr(qsorted), int(nq), _ptr(adev), a.shape[0],
+                                               _ptr(bdev), b.shape[0], PAIRS2D_MODES[mode], int(los),
+                                               None if period is None else _period_c(period), _ptr(out_perm),
+                                               _ptr(res), _ptr(stats), _stream(tree[0])), "pair_counts_2d")
+    return res
+
+
 # --------------------------------------------------------------------------- weighted radius profiles
 def int64_weights(what: str, name: str, w, count: int, device: torch.device | None = None) -> torch.Tensor:
     """The int64 [count] weight tensor `name` of the function `what`, checked and contiguous (also

@@ -6,6 +6,8 @@
                                    [--period L | Lx,Ly,Lz]
     python scripts/radius_bench.py --profile B [-r R] [--self-queries] [--points ..] [--queries ..] [--mean ..]
                                    [--steps ..] [--warmup ..] [--period ..] [--weights]
+    python scripts/radius_bench.py --pairs-2d BPxBL [--smu] [-r R] [--self-queries] [--points ..] [--queries ..]
+                                   [--steps ..] [--warmup ..] [--period ..] [--skip-pair-list]
 
 Uniform points in the unit cube and uniform queries from another seed; the radius is the one
 whose ball holds --mean points at the data's density (queries near the faces see fewer, so
@@ -44,6 +46,15 @@ by id and a segment sum in torch. The JSON carries the medians and the radius_* 
 weighted and the unweighted walk (equal when B fits one slice of both kernels: the walks are the
 same); the weighted profile's last column is compared with the pair-list route, its column sums
 with the pair sums, before anything is reported.
+
+--pairs-2d BPxBL: the anisotropic pair counts. BP x BL linearly spaced edges up to R (-r, default
+0.01) across and along the line of sight z (--smu: BP separations up to R and BL cosines up to 1),
+timed alternately in one process: one pair_counts_rppi (pair_counts_smu) call; pair_counts with BP
+radii up to the enclosing radius (sqrt(2) R; --smu: R), the floor of what one walk costs; and the
+route without the kernel: radius_neighbors(sort=False) at the enclosing radius in query chunks that
+respect max_pairs, the differences re-derived and binned in torch (its cells are compared with the
+kernel's and the number that differ is reported: torch promises no fma). The JSON carries the
+medians and the radius_* counters of the two walks.
 """
 from __future__ import annotations
 
@@ -185,6 +196,96 @@ def weighted_bench(a, p: torch.Tensor, q: torch.Tensor, r: float, per: dict) -> 
     return 0 if same_list and same_sums else 1
 
 
+def pair_list_cells(index, p, q, R, first2, second2, smu: bool, per: dict, period, chunk: int) -> torch.Tensor:
+    """The differential [B1, B2] cells (int64) by way of the pair lists at the enclosing radius R."""
+    b1, b2 = first2.shape[0], second2.shape[0]
+    cells = torch.zeros(b1 * b2, dtype=torch.int64, device=q.device)
+    for a in range(0, q.shape[0], chunk):
+        offsets, idx, _ = E.radius_neighbors(index, q[a:a + chunk], R, sort=False, **per)
+        rows = torch.repeat_interleave(torch.arange(a, a + offsets.shape[0] - 1, device=q.device),
+                                       offsets[1:] - offsets[:-1])
+        d = q[rows] - p[idx.long()]
+        if period is not None:
+            for ax in range(3):
+                L = period[ax]
+                if math.isfinite(L):
+                    x = d[:, ax]
+                    d[:, ax] = torch.where(x > 0.5 * L, x - L, torch.where(x < -0.5 * L, x + L, x))
+        par2 = d[:, 2] * d[:, 2]
+        perp2 = torch.addcmul(d[:, 0] * d[:, 0], d[:, 1], d[:, 1])
+        if smu:
+            d2 = perp2 + par2
+            i0 = torch.bucketize(d2, first2, right=True)
+            j0 = b2 - (par2[:, None] < second2[None, :] * d2[:, None]).sum(1)
+        else:
+            i0 = torch.bucketize(perp2, first2, right=True)
+            j0 = torch.bucketize(par2, second2, right=True)
+        ok = (i0 < b1) & (j0 < b2)
+        cells += torch.bincount((i0 * b2 + j0)[ok], minlength=b1 * b2)
+    return cells.view(b1, b2)
+
+
+def pairs2d_bench(a, p: torch.Tensor, q: torch.Tensor, per: dict) -> int:
+    """--pairs-2d BPxBL [--smu]: the kernel, the isotropic pair counts as the floor, the pair-list route."""
+    b1, b2 = (int(v) for v in a.pairs_2d.lower().split("x"))
+    R = a.radius if a.radius is not None else 0.01
+    first = [R * (i + 1) / b1 for i in range(b1)]
+    second = [(1.0 if a.smu else R) * (j + 1) / b2 for j in range(b2)]
+    Renc = R if a.smu else math.sqrt(2.0) * R * (1.0 + 1e-6)
+    fn2d = E.pair_counts_smu if a.smu else E.pair_counts_rppi
+    index = E.build_index(p)
+    first2 = torch.tensor([E.cut2_of(v) for v in first], device=p.device)
+    second2 = torch.tensor([E.cut2_of(v) for v in second], device=p.device)
+    mean = q.shape[0] and p.shape[0] * 4.0 / 3.0 * math.pi * Renc ** 3
+    chunk = max(1, int((1 << (24 if a.smu else 26)) / max(mean, 1.0)))
+    out = {}
+    cases = {
+        "pairs2d": lambda **kw: out.__setitem__("pairs2d", fn2d(index, q, first, second, **per, **kw)),
+        "pairs1d": lambda **kw: out.__setitem__(
+            "pairs1d", E.pair_counts(index, q, [Renc * (i + 1) / b1 for i in range(b1)], **per, **kw)),
+    }
+    if not a.skip_pair_list:
+        cases["pair_list"] = lambda: out.__setitem__(
+            "list", pair_list_cells(index, p, q, Renc, first2, second2, a.smu, per, a.period, chunk))
+    times = {name: [] for name in cases}
+    for step in range(a.warmup + a.steps):
+        for name, fn in cases.items():
+            out.clear()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            if step >= a.warmup:
+                times[name].append(time.perf_counter() - t0)
+    med = {name: statistics.median(ts) for name, ts in times.items()}
+    counters = {}
+    out.clear()
+    for name, fn in cases.items():
+        if name == "pair_list":
+            fn()
+            continue
+        st = E.KnnStats()
+        fn(stats=st)
+        counters[name] = dict(st.counters)
+    S = out["pairs2d"]
+    rec = {
+        "points": p.shape[0], "queries": q.shape[0], "self_queries": bool(a.self_queries),
+        "mode": "smu" if a.smu else "rppi", "grid": [b1, b2], "R": R, "enclosing_radius": Renc,
+        "pairs_in_grid": int(S[-1, -1]), "steps": a.steps, "warmup": a.warmup,
+        "lib": os.environ.get("LSKNN_HIP_LIB", ""),
+        "pairs2d_s": med["pairs2d"], "pairs1d_s": med["pairs1d"], "pair_list_s": med.get("pair_list"),
+        "spread": {name: [min(ts), max(ts)] for name, ts in times.items()}, "counters": counters,
+    }
+    if "list" in out:
+        rec["pair_list_chunk"] = chunk
+        rec["pair_list_cells_differing"] = int((E.shell_counts_2d(S) != out["list"]).sum())
+        rec["pair_list_total"] = int(out["list"].sum())
+    if a.period is not None:
+        rec["period"] = list(a.period)
+    print(json.dumps(rec), flush=True)
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=float, default=1e7)
@@ -199,9 +300,15 @@ def main() -> int:
     ap.add_argument("-r", dest="radius", type=float, default=None, help="--profile: the largest radius")
     ap.add_argument("--self-queries", action="store_true", help="--profile: the points are their own queries")
     ap.add_argument("--weights", action="store_true", help="--profile: the weighted profile and its alternatives")
+    ap.add_argument("--pairs-2d", default=None, metavar="BPxBL", help="time the anisotropic pair counts instead")
+    ap.add_argument("--smu", action="store_true", help="--pairs-2d: the (s, mu) mode")
+    ap.add_argument("--skip-pair-list", action="store_true", help="--pairs-2d: without the pair-list route")
     add_period_option(ap)
     a = ap.parse_args()
-    if a.profile < 0 or (a.profile == 0 and (a.radius is not None or a.self_queries or a.weights)):
+    if a.pairs_2d is None and (a.smu or a.skip_pair_list):
+        ap.error("--smu and --skip-pair-list belong to --pairs-2d")
+    if a.profile < 0 or (a.profile == 0 and a.pairs_2d is None and
+                         (a.radius is not None or a.self_queries or a.weights)):
         ap.error("--profile B needs B >= 1; -r, --self-queries and --weights belong to it")
     if a.period is not None and a.radii == "point-kth":
         ap.error("--period is not supported with --radii point-kth")
@@ -214,6 +321,8 @@ def main() -> int:
     p = torch.rand((n, 3), generator=torch.Generator(device=dev).manual_seed(1), device=dev)
     q = torch.rand((nq, 3), generator=torch.Generator(device=dev).manual_seed(2), device=dev)
     r = (k / (n * 4.0 / 3.0 * math.pi)) ** (1.0 / 3.0)
+    if a.pairs_2d is not None:
+        return pairs2d_bench(a, p, p if a.self_queries else q, per)
     if a.profile:
         bench = weighted_bench if a.weights else profile_bench
         return bench(a, p, p if a.self_queries else q, a.radius if a.radius is not None else r, per)
