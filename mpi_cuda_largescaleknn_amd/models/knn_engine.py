@@ -175,6 +175,13 @@ FRAME_EARLY = os.environ.get("LSKNN_FRAME_EARLY", "1") == "1"
 # ... and only while the plane's k-NN radius (sqrt(k * area / (pi * n))) is >= FRAME_RADIUS_X
 # times the boxes' widening (rotate_margin); measured wins down to a ratio of ~4 (5e8, k = 48).
 FRAME_RADIUS_X = float(os.environ.get("LSKNN_FRAME_RADIUS_X", "2"))
+# ... and only while the square of that widening is a normal float32. A rotated box culls by
+# its float32 squared distance against canonical squared distances; the widening m covers the
+# two frames' difference by leaving d2 - gap2 >= (m / 2)^2. Below the normal range a squared
+# distance rounds by an absolute 2^-150 per operation instead of a relative 2^-24, and once
+# m^2 is down there the rounding outweighs the widening: a box that holds the k-th neighbour
+# is culled (coordinates of ~2^-70: 4 of 20 000 k = 100 distances of a tilted plane wrong).
+FRAME_MIN_MARGIN2 = 2.0 ** -126
 # Curve keys in the plane's frame: above PLANE_2D_MIN points, 2-D Morton keys of the two
 # in-plane coordinates, 15 bits each — 3-D keys spend a third of their 30 bits on the flat
 # axis: 1024^2 cells, ~200 points each at 2e8, wider than the k-NN radius (tilted plane,
@@ -254,7 +261,8 @@ class FrameProbe:
         # the k-NN radius against rotate_margin (extents of a uniform spread: sqrt(12 var))
         e1, e2 = math.sqrt(12.0 * w[1] / self.m), math.sqrt(12.0 * w[2] / self.m)
         radius = math.sqrt(self.k * e1 * e2 / (math.pi * max(self.n, 1)))
-        if radius < FRAME_RADIUS_X * (a[6] * 1.7320508 + e2) * 2.0 ** -16:
+        margin = (a[6] * 1.7320508 + e2) * 2.0 ** -16
+        if radius < FRAME_RADIUS_X * margin or margin * margin < FRAME_MIN_MARGIN2:
             return None
         R = v[:, ::-1].T.copy()  # rows: axes by decreasing variance
         return torch.tensor(R, dtype=torch.float32, device=self.device)

@@ -81,8 +81,21 @@ def pairs_within(points, cut2, period=None):
 
 
 def _labels(p, cut2, min_pts, period):
-    n = p.shape[0]
-    a, b, d2 = pairs_within(p, cut2, period)
+    return _labels_of_pairs(p.shape[0], *pairs_within(p, cut2, period), min_pts)
+
+
+def dense_labels(weights, cut2, min_pts):
+    """dbscan_labels from the all-pairs weights (float32 [n, n], symmetric, 0 on the diagonal)
+    instead of a k-d tree, for inputs the tree does not take: coordinates outside [0, period),
+    squared distances that are denormal or overflow. cut2 > 0, so every point links to itself."""
+    w = np.asarray(weights, dtype=np.float32)
+    assert np.float32(cut2) > 0 and w.ndim == 2 and w.shape[0] == w.shape[1]
+    a, b = np.triu_indices(w.shape[0], k=1)
+    keep = w[a, b] < np.float32(cut2)
+    return _labels_of_pairs(w.shape[0], a[keep], b[keep], w[a, b][keep], int(min_pts))
+
+
+def _labels_of_pairs(n, a, b, d2, min_pts):
     # a point is linked to itself and its exact copies (d2 = 0 < cut2); the copies are pairs
     counts = 1 + np.bincount(a, minlength=n) + np.bincount(b, minlength=n)
     core = counts >= min_pts
