@@ -49,4 +49,6 @@ from .models.knn_engine import (KnnConfig, build_index, cluster_labels, cluster_
                                 weighted_self_profile, weighted_pair_sums, weighted_pair_query_sums,
                                 weighted_pair_self_sums, mst_edges, mst_points, mst_labels,
                                 pair_counts_rppi, pair_query_counts_rppi, pair_self_counts_rppi, pair_counts_smu,
-                                pair_query_counts_smu, pair_self_counts_smu, shell_counts_2d)
+                                pair_query_counts_smu, pair_self_counts_smu, shell_counts_2d, weighted_pair_sums_rppi,
+                                weighted_pair_query_sums_rppi, weighted_pair_self_sums_rppi,
+                                weighted_pair_sums_smu, weighted_pair_query_sums_smu, weighted_pair_self_sums_smu)

@@ -1,8 +1,8 @@
 """hipKNN_pairs — anisotropic pair counts along a line of sight: DD(rp, pi) and DD(s, mu).
 
     hipKNN_pairs <points.float3> <queries.float3> (--rp R1,R2,... --pi P1,P2,... | --s S1,S2,... --mu M1,M2,...)
-                 [--los x|y|z] [--squared] [--period L | Lx,Ly,Lz] [--chunk N] [--device auto|cuda|cpu]
-                 [--stats f.json] [-v] -o <PREFIX>
+                 [--los x|y|z] [--squared] [--period L | Lx,Ly,Lz] [--weights W.i64 [--query-weights WQ.i64]]
+                 [--chunk N] [--device auto|cuda|cpu] [--stats f.json] [-v] -o <PREFIX>
 
 For every pair (row of the query file, row of the point file) the float32 differences q - p, with
 --period their minimum image, are split along the line of sight --los (a box axis, default z):
@@ -20,6 +20,14 @@ PREFIX.pairs2d holds the counts, headerless int64 [B1][B2], row-major. One line 
 is printed: the first-axis edge, then the row's binned (not cumulative) counts. The index over the
 points is built once; the queries go through it in chunks of --chunk rows whose counts are added
 on the host. One process, one device.
+
+--weights W.i64: a headerless little-endian int64 file, one weight per row of the point file,
+negative allowed; --query-weights WQ.i64: the same per row of the query file (without it every
+query weighs 1). Every pair then adds wq * w in the place of 1 and the result goes to
+PREFIX.wpairs2d (int64 [B1][B2], cumulative; PREFIX.pairs2d is not written), the printed rows hold
+the binned sums. The sums are exact: max|w| * n must be below 2^62 and (sum |w|) * (sum |wq|) (the
+number of queries without --query-weights) below 2^63, checked over the whole query file before the
+first chunk. lsknn_tools fixweights turns float masses into such weights.
 """
 from __future__ import annotations
 
@@ -34,7 +42,7 @@ from ..models import knn_engine as E
 from ..parallel import launch as L
 from ..utils import io
 from .query import _device
-from .radius import add_period_option
+from .radius import add_period_option, read_weights
 
 
 def edges_arg(name: str):
@@ -59,6 +67,10 @@ def add_pairs_options(ap: argparse.ArgumentParser) -> None:
     ap.add_argument("--los", choices=["x", "y", "z"], default="z", help="the line-of-sight axis (default z)")
     ap.add_argument("--squared", action="store_true", help="--rp / --pi / --s are squared cutoffs")
     add_period_option(ap)
+    ap.add_argument("--weights", default=None, metavar="W.i64",
+                    help="headerless int64 file, one weight per point row: the sums of wq * w (PREFIX.wpairs2d)")
+    ap.add_argument("--query-weights", default=None, metavar="WQ.i64",
+                    help="with --weights: headerless int64 file, one weight per query row")
 
 
 def pairs_mode(ap: argparse.ArgumentParser, a: argparse.Namespace) -> None:
@@ -69,6 +81,8 @@ def pairs_mode(ap: argparse.ArgumentParser, a: argparse.Namespace) -> None:
         ap.error("exactly one of: --rp with --pi, --s with --mu")
     a.mode = "rppi" if rppi else "smu"
     a.first, a.second = (a.rp, a.pi) if rppi else (a.s, a.mu)
+    if a.query_weights is not None and a.weights is None:
+        ap.error("--query-weights needs --weights")
 
 
 def parse(argv: list[str]) -> argparse.Namespace:
@@ -76,7 +90,7 @@ def parse(argv: list[str]) -> argparse.Namespace:
     ap.add_argument("points", help="float3 file: the point set")
     ap.add_argument("queries", help="float3 file: the query positions")
     add_pairs_options(ap)
-    ap.add_argument("-o", dest="out", required=True, metavar="PREFIX", help="writes PREFIX.pairs2d")
+    ap.add_argument("-o", dest="out", required=True, metavar="PREFIX", help="writes PREFIX.pairs2d (--weights: PREFIX.wpairs2d)")
     ap.add_argument("--chunk", type=int, default=1 << 24, help="queries per pass (default 2^24)")
     ap.add_argument("--device", choices=["auto", "cuda", "cpu"], default="auto")
     ap.add_argument("--stats", default="", help="write run statistics to this JSON file")
@@ -109,19 +123,32 @@ def main(argv: list[str] | None = None) -> int:
     sync()
     t1 = time.perf_counter()
     nq = io.portion(a.queries, 0, 1)[2]
-    fn = E.pair_counts_rppi if a.mode == "rppi" else E.pair_counts_smu
+    weighted = a.weights is not None
+    if weighted:
+        fn = E.weighted_pair_sums_rppi if a.mode == "rppi" else E.weighted_pair_sums_smu
+    else:
+        fn = E.pair_counts_rppi if a.mode == "rppi" else E.pair_counts_smu
     b1, b2 = len(a.first), len(a.second)
     total = [[0] * b2 for _ in range(b1)]  # Python ints: no overflow however many chunks
     try:
+        if weighted:  # the weights once, and the whole file's bound: PREFIX.wpairs2d holds int64
+            pw = E.prepare_point_weights(index, read_weights(a.weights, "--weights", index.n, a.points).to(dev))
+            wq = None if a.query_weights is None else read_weights(a.query_weights, "--query-weights", nq, a.queries)
+            E.check_pair_sum_bound("--weights", pw, wq, nq)
         for begin in range(0, nq, a.chunk):
             q = io.read_range(a.queries, begin, min(a.chunk, nq - begin), pin_memory=gpu).to(dev)
-            part = fn(index, q, a.first, a.second, los=a.los, squared=a.squared, stats=stats, **per).cpu().tolist()
-            total = [[s + int(v) for s, v in zip(row, prow)] for row, prow in zip(total, part)]
+            if weighted:
+                wqc = None if wq is None else wq[begin:begin + q.shape[0]].to(dev)
+                part = fn(index, q, a.first, a.second, pw, query_weights=wqc, los=a.los, squared=a.squared,
+                          stats=stats, **per)
+            else:
+                part = fn(index, q, a.first, a.second, los=a.los, squared=a.squared, stats=stats, **per)
+            total = [[s + int(v) for s, v in zip(row, prow)] for row, prow in zip(total, part.cpu().tolist())]
     except ValueError as e:
         sys.stderr.write(f"hipKNN_pairs: {e}\n")
         return 1
     S = torch.tensor(total, dtype=torch.int64).reshape(b1, b2)
-    io.write_array(a.out + ".pairs2d", S.reshape(-1), 0, truncate=True, total=b1 * b2)
+    io.write_array(a.out + (".wpairs2d" if weighted else ".pairs2d"), S.reshape(-1), 0, truncate=True, total=b1 * b2)
     for edge, row in zip(a.first, E.shell_counts_2d(S).tolist()):
         print(f"{edge!r} " + " ".join(str(v) for v in row), flush=True)
     sync()
@@ -133,6 +160,10 @@ def main(argv: list[str] | None = None) -> int:
         rec = {"n": index.n, "nq": nq, "mode": a.mode, "first": a.first, "second": a.second, "los": a.los,
                "pairs": total, "chunk": a.chunk, "device": str(dev), "index_s": t1 - t0, "query_s": t2 - t1,
                "kernels": E.kernels_used(), "radius_search": stats.counters}
+        if weighted:
+            rec["weights"] = a.weights
+            if a.query_weights is not None:
+                rec["query_weights"] = a.query_weights
         if a.squared:
             rec["squared"] = True
         if a.period is not None:

@@ -23,9 +23,9 @@
            -> hipKNN_radius --profile --weights' PREFIX.wprofile and PREFIX.wpairs against the oracle, on
               the same sampling rules
     python -m mpi_cuda_largescaleknn_amd.apps.tools pcheck in.float3 q.float3 PREFIX (--rp .. --pi .. | --s .. --mu ..)
-           [--los x|y|z] [--squared] [--period L | Lx,Ly,Lz]
-           -> hipKNN_pairs' PREFIX.pairs2d against the brute-force oracle, every cell (at most 65536
-              queries: the oracle visits every pair)
+           [--los x|y|z] [--squared] [--period L | Lx,Ly,Lz] [--weights W.i64 [--query-weights WQ.i64]]
+           -> hipKNN_pairs' PREFIX.pairs2d (--weights: PREFIX.wpairs2d) against the brute-force oracle,
+              every cell (at most 65536 queries: the oracle visits every pair)
     python -m mpi_cuda_largescaleknn_amd.apps.tools fixweights in.float out.i64 [--bits N] [--terms T]
            -> float32 masses as exact fixed-point int64 weights
               (knn_engine.fixed_point_weights); prints the exponent s: physical sum = result * 2^s
@@ -196,7 +196,7 @@ def _rcheck_profile(a, pts, qry) -> int:
 
 
 def pcheck(a) -> int:
-    """PREFIX.pairs2d of hipKNN_pairs against the oracle, every cell."""
+    """PREFIX.pairs2d (--weights: PREFIX.wpairs2d) of hipKNN_pairs against the oracle, every cell."""
     from ..models.knn_engine import _pairs2d_cutoffs
     try:
         a2, b2, los, per = _pairs2d_cutoffs("pcheck", a.mode, a.first, a.second, a.los, a.squared, a.period)
@@ -208,16 +208,30 @@ def pcheck(a) -> int:
         print(f"pcheck: {qry.shape[0]} queries, more than {CCHECK_MAX}: the oracle visits every pair; check a "
               "smaller set")
         return 1
-    got = io.read_array(a.prefix + ".pairs2d", torch.int64)
+    weighted = a.weights is not None
+    if weighted:
+        from .radius import read_weights
+        try:
+            w = read_weights(a.weights, "--weights", pts.shape[0], a.inp)
+            wq = None if a.query_weights is None else \
+                read_weights(a.query_weights, "--query-weights", qry.shape[0], a.queries)
+        except ValueError as e:
+            print(f"pcheck: {e}")
+            return 1
+    name = "WPAIRS2D" if weighted else "PAIRS2D"
+    got = io.read_array(a.prefix + ("." + name.lower()), torch.int64)
     if got.shape[0] != a2.shape[0] * b2.shape[0]:
         print(f"size mismatch: {got.shape[0]} cells for {a2.shape[0]} x {b2.shape[0]} edges")
         return 1
     got = got.view(a2.shape[0], b2.shape[0])
-    ref = K.pair_counts_2d_cpu(pts, qry, a2, b2, a.mode, los, per)
+    if weighted:
+        ref = K.weighted_pair_sums_2d_cpu(pts, qry, a2, b2, w, a.mode, los, per, query_weights=wq)
+    else:
+        ref = K.pair_counts_2d_cpu(pts, qry, a2, b2, a.mode, los, per)
     wrong = (got != ref).nonzero()
     print(f"checked {ref.numel()} cells: {wrong.shape[0]} mismatches")
     for i, j in wrong[:10].tolist():
-        print(f"PAIRS2D [{i}][{j}] = {int(got[i, j])} (oracle {int(ref[i, j])})")
+        print(f"{name} [{i}][{j}] = {int(got[i, j])} (oracle {int(ref[i, j])})")
     return 0 if wrong.shape[0] == 0 else 1
 
 

@@ -78,6 +78,29 @@
 // atomic add (the host zeroes the result first); there is no [blocks, cells] workspace. Integer
 // sums: the result does not depend on the order, two runs give the same bits. A last small kernel
 // turns the differential cells into the cumulative array in place.
+//
+// Weighted sums (lsk_hip_weighted_pair_sums_2d): WS[i, j] = the sum of wq[q] * w[p] over the pairs
+// S[i, j] counts. The same kernel under a policy (CountPolicy, WeightPolicy below), as in
+// radius_profile.hip; the walk is untouched, so both policies visit the same nodes, scan the same
+// buckets and accept the same boxes (their stats are equal), and with every weight 1 the sums are
+// the counts, bit for bit. Four places differ.
+//  * Query weight: each lane loads wq[Q.row] once after load_group, as wrapping u64; 1 without wq.
+//    The multiply by that 1 stays: a template flag that drops it would save no register the
+//    allocation can use and the whole policy costs 4 - 12 % (docs/ARCHITECTURE.md), so the second
+//    set of four instances was not built.
+//  * Candidates: the weights travel in curve order as the scan's column (lsk::WeightCol, two
+//    32-bit readlanes per point); a counting lane adds wq * w to its cell by the same 64-bit LDS
+//    atomic add.
+//  * Whole-box acceptance, (rp, pi): the lane adds wq * (wpre[p1] - wpre[p0]) over the node's
+//    sorted positions [p0, p1) (node_span), wpre [n + 1] being the exclusive prefix sum of the
+//    sorted weights: no weight read per point, no distance evaluation. The proof above is about
+//    WHICH cell a point falls in, not about what is added there. "Below the slice" is unchanged.
+//  * End of block and cumulate are the wrapping u64 adds they were (a cell whose weights cancel
+//    to zero is skipped like an empty one).
+// Exactness is that of radius_profile.hip ("What the weight policy changes"): the host admits only
+// max|w| * n < 2^62 and (sum |w|) * (sum |wq|) < 2^63, every cell, partial sum and cumulative
+// entry is a sum of wq * w over a subset of the pairs, so wrapping 64-bit arithmetic in any order
+// gives the true value, and two runs give the same bits.
 #include <algorithm>
 
 #include "periodic_image.h"
@@ -106,6 +129,37 @@ struct Pair2dArgs {
   const uint32_t *out_perm;  // sorted query -> query row
   u64 *out;                  // [na, nb] differential cells, zeroed by the host
   u64 *stats;                // optional [4] (kPeriodic: [5]), as radius_profile.hip
+};
+
+struct WeightedPair2dArgs : Pair2dArgs {
+  const int64_t *wsorted;  // [n] point weights in curve order
+  const int64_t *wpre;     // [n + 1] exclusive prefix sum of wsorted
+  const int64_t *wq;       // optional [nq] query weights, query order
+};
+
+// What a pair adds to its cell. args: the kernel's argument block; column: what travels with a
+// candidate through the scan; query(A, Q): the lane's factor, loaded once; of(f, its value): what
+// a candidate adds; node(A, f, p0, p1): what a node accepted whole adds for its sorted positions
+// [p0, p1).
+struct CountPolicy {
+  typedef Pair2dArgs args;
+  static __device__ __forceinline__ lsk::NoCol column(const args &) { return {}; }
+  static __device__ __forceinline__ u64 query(const args &, const lsk::GroupQuery &) { return 1ull; }
+  static __device__ __forceinline__ u64 of(u64, lsk::NoCol::value) { return 1ull; }
+  static __device__ __forceinline__ u64 node(const args &, u64, int64_t p0, int64_t p1) { return (u64)(p1 - p0); }
+};
+
+struct WeightPolicy {
+  typedef WeightedPair2dArgs args;
+  static __device__ __forceinline__ lsk::WeightCol column(const args &A) { return {A.wsorted}; }
+  // (a lane without a query adds nothing anyway)
+  static __device__ __forceinline__ u64 query(const args &A, const lsk::GroupQuery &Q) {
+    return Q.valid && A.wq ? (u64)A.wq[Q.row] : 1ull;
+  }
+  static __device__ __forceinline__ u64 of(u64 f, u64 w) { return f * w; }
+  static __device__ __forceinline__ u64 node(const args &A, u64 f, int64_t p0, int64_t p1) {
+    return f * ((u64)A.wpre[p1] - (u64)A.wpre[p0]);
+  }
 };
 
 // The three per-axis values ordered by the line of sight: (along, first other, second other).
@@ -168,8 +222,8 @@ __device__ __forceinline__ float open_far(float q, float lo, float hi) {
 }
 
 // kSmu: (s, mu) mode, else (rp, pi).
-template <bool kPeriodic, bool kSmu>
-__global__ __launch_bounds__(kWaves * 64) void pair_counts_2d_walk_kernel(const Pair2dArgs A) {
+template <bool kPeriodic, bool kSmu, class Policy>
+__global__ __launch_bounds__(kWaves * 64) void pair_counts_2d_walk_kernel(const typename Policy::args A) {
   __shared__ uint32_t stk_all[kWaves][lsk::kWalkStack];
   __shared__ u64 cells[kCells];
   __shared__ float ca[kMaxEdges + 1];  // the slice's first-axis cutoffs, after the one below it
@@ -192,6 +246,7 @@ __global__ __launch_bounds__(kWaves * 64) void pair_counts_2d_walk_kernel(const 
   lsk::GroupQuery Q{0, 0, 0.f, 0.f, 0.f, false, false};
   if (active) Q = lsk::load_group(g, lane, A.qpts, A.out_perm, A.nq);
   const bool live = Q.finite && amax > 0.f && bmax > 0.f;
+  const u64 fq = Policy::query(A, Q);  // the lane's query weight
   lsk::Cover cov;  // the whole node the lane took
   uint32_t s_evals = 0, s_accepts = 0, s_nodes = 0, s_buckets = 0, s_images = 0;
   const lsk_tree_view &T = A.T;
@@ -199,9 +254,9 @@ __global__ __launch_bounds__(kWaves * 64) void pair_counts_2d_walk_kernel(const 
   // row index within ca of a first-axis value v < amax; column of a par2 < bmax (rp, pi)
   auto row_of = [&](float v) { return first_of(ma, sa, [&](uint32_t i) { return v < ca[i]; }); };
   auto col_of = [&](float v) { return first_of(nb, sb, [&](uint32_t j) { return v < cb[j]; }); };
-  // a counting lane (`on`) adds 1 to its cell
-  auto count = [&](bool on, uint32_t cell) {
-    if (on) atomicAdd(&cells[cell], 1ull);
+  // a counting lane (`on`) adds what the policy has for the candidate to its cell
+  auto count = [&](bool on, uint32_t cell, auto w) {
+    if (on) atomicAdd(&cells[cell], Policy::of(fq, w));
   };
   // (rp, pi): near_perp2 < amax, near_par2 < bmax. The whole node in one cell, or below the slice.
   auto accept = [&](uint32_t node, int32_t lvl, uint32_t sp, float np2, float nl2, float fp2, float fl2) {
@@ -213,7 +268,7 @@ __global__ __launch_bounds__(kWaves * 64) void pair_counts_2d_walk_kernel(const 
       if (col_of(nl2) != cf) return false;
       int64_t p0, p1;
       lsk::node_span(T, node, lvl, p0, p1);
-      if (p1 > p0) atomicAdd(&cells[(rf - below) * nb + cf], (u64)(p1 - p0));
+      if (p1 > p0) atomicAdd(&cells[(rf - below) * nb + cf], Policy::node(A, fq, p0, p1));
     }
     cov.take(sp);
     s_accepts++;
@@ -223,7 +278,7 @@ __global__ __launch_bounds__(kWaves * 64) void pair_counts_2d_walk_kernel(const 
   // a bucket: the lanes that need it put its points into their cells one by one
   auto scan = [&](uint32_t node, bool use, const auto &diff) {
     const bool evals = use;
-    const int cnt = lsk::scan_bucket(T, node, lane, Q, diff, lsk::NoCol{}, lsk::NoCol{}, use,
+    const int cnt = lsk::scan_bucket(T, node, lane, Q, diff, Policy::column(A), lsk::NoCol{}, use,
                                      [&](const auto &c, bool &) {
                                        const float va = kSmu ? c.d2 : perp2;
                                        bool on = c.mine && va < amax;
@@ -246,7 +301,7 @@ __global__ __launch_bounds__(kWaves * 64) void pair_counts_2d_walk_kernel(const 
                                            cell = (r - below) * nb + col_of(par2);
                                          }
                                        }
-                                       count(on, cell);
+                                       count(on, cell, c.a);
                                      });
     if (cnt) s_buckets++;
     if (evals) s_evals += (uint32_t)cnt;
@@ -365,23 +420,21 @@ __global__ __launch_bounds__(kCumThreads) void pair_counts_2d_cumulate_kernel(u6
   }
 }
 
-template <bool kPeriodic>
-void launch_walk(const Pair2dArgs &A, bool smu, unsigned blocks, hipStream_t st) {
+template <bool kPeriodic, class Policy>
+void launch_walk(const typename Policy::args &A, bool smu, unsigned blocks, hipStream_t st) {
   if (smu)
-    pair_counts_2d_walk_kernel<kPeriodic, true><<<blocks, kWaves * 64, 0, st>>>(A);
+    pair_counts_2d_walk_kernel<kPeriodic, true, Policy><<<blocks, kWaves * 64, 0, st>>>(A);
   else
-    pair_counts_2d_walk_kernel<kPeriodic, false><<<blocks, kWaves * 64, 0, st>>>(A);
+    pair_counts_2d_walk_kernel<kPeriodic, false, Policy><<<blocks, kWaves * 64, 0, st>>>(A);
 }
 
-}  // namespace
-
-extern "C" int lsk_hip_pair_counts_2d_cells(void) { return kCells; }
-
-extern "C" int lsk_hip_pair_counts_2d(const lsk_tree_view *tree, const float *qpts, int64_t nq, const float *a2,
-                                      int32_t na, const float *b2, int32_t nb, int32_t mode, int32_t los,
-                                      const float *period, const uint32_t *out_perm, int64_t *out,
-                                      unsigned long long *stats, void *stream) {
-  const char *what = "pair_counts_2d";
+// What the two entry points share: the argument checks, the zeroed result, one walk per slice of
+// rows and the cumulate. A: the policy's arguments, its own fields set by the caller.
+template <class Policy>
+int run_pairs_2d(const char *what, typename Policy::args &A, const lsk_tree_view *tree, const float *qpts,
+                 int64_t nq, const float *a2, int32_t na, const float *b2, int32_t nb, int32_t mode, int32_t los,
+                 const float *period, const uint32_t *out_perm, int64_t *out, unsigned long long *stats,
+                 void *stream) {
   if (!lsk_tree_ok(tree) || nq < 0 || nq >= ((int64_t)1 << 32) || na < 1 || na > kMaxEdges || nb < 1 ||
       nb > kMaxEdges || (int64_t)na * nb > kMaxGrid || mode < 0 || mode > 1 || los < 0 || los > 2) {
     lsk::set_last_error(std::string(what) + ": tree view incomplete (1 <= n < 2^31, depth = tree_depth(n)), "
@@ -389,7 +442,6 @@ extern "C" int lsk_hip_pair_counts_2d(const lsk_tree_view *tree, const float *qp
                         ", na * nb > " + std::to_string(kMaxGrid) + ", mode not 0 / 1 or los not 0 / 1 / 2");
     return 1;
   }
-  Pair2dArgs A{};
   for (int a = 0; a < 3; a++) {
     A.L[a] = period ? period[a] : __builtin_inff();
     if (!(A.L[a] > 0.f)) {
@@ -421,12 +473,43 @@ extern "C" int lsk_hip_pair_counts_2d(const lsk_tree_view *tree, const float *qp
     A.r0 = r0;
     A.r1 = std::min(na, r0 + rows);
     if (period)
-      launch_walk<true>(A, mode == 1, blocks, st);
+      launch_walk<true, Policy>(A, mode == 1, blocks, st);
     else
-      launch_walk<false>(A, mode == 1, blocks, st);
+      launch_walk<false, Policy>(A, mode == 1, blocks, st);
     LSK_CHECK_LAUNCH(what);
   }
   pair_counts_2d_cumulate_kernel<<<1, kCumThreads, 0, st>>>(A.out, na, nb);
   LSK_CHECK_LAUNCH(std::string(what) + " (cumulate)");
   return 0;
+}
+
+}  // namespace
+
+extern "C" int lsk_hip_pair_counts_2d_cells(void) { return kCells; }
+
+extern "C" int lsk_hip_pair_counts_2d(const lsk_tree_view *tree, const float *qpts, int64_t nq, const float *a2,
+                                      int32_t na, const float *b2, int32_t nb, int32_t mode, int32_t los,
+                                      const float *period, const uint32_t *out_perm, int64_t *out,
+                                      unsigned long long *stats, void *stream) {
+  Pair2dArgs A{};
+  return run_pairs_2d<CountPolicy>("pair_counts_2d", A, tree, qpts, nq, a2, na, b2, nb, mode, los, period, out_perm,
+                                   out, stats, stream);
+}
+
+extern "C" int lsk_hip_weighted_pair_sums_2d(const lsk_tree_view *tree, const float *qpts, int64_t nq,
+                                             const float *a2, int32_t na, const float *b2, int32_t nb,
+                                             int32_t mode, int32_t los, const float *period,
+                                             const uint32_t *out_perm, const int64_t *wsorted, const int64_t *wpre,
+                                             const int64_t *wq, int64_t *out, unsigned long long *stats,
+                                             void *stream) {
+  if (nq > 0 && (!wsorted || !wpre)) {
+    lsk::set_last_error("weighted_pair_sums_2d: null argument");
+    return 1;
+  }
+  WeightedPair2dArgs A{};
+  A.wsorted = wsorted;
+  A.wpre = wpre;
+  A.wq = wq;
+  return run_pairs_2d<WeightPolicy>("weighted_pair_sums_2d", A, tree, qpts, nq, a2, na, b2, nb, mode, los, period,
+                                    out_perm, out, stats, stream);
 }

@@ -537,9 +537,10 @@ extern "C" void lsk_cpu_weighted_profile(const float *pts, int64_t n, const floa
 // j0 = #{j : !(par2 < b2[j])}; mode 1, (s, mu): i0 = #{i : !(d2 < a2[i])}, j0 = #{j : !(par2 <
 // b2[j] * d2)} (one float32 product). A pair with i0 == na or j0 == nb is dropped. Every thread
 // counts differential cells of its own; out [na, nb] is the 2-D prefix sum of their total.
-extern "C" void lsk_cpu_pair_counts_2d(const float *pts, int64_t n, const float *qry, int64_t nq, const float *a2,
-                                       int32_t na, const float *b2, int32_t nb, int mode, int los,
-                                       const float *period, int64_t *out, int nthreads) {
+// w (with wq: optional) null: every pair adds 1; else wq[q] * w[i] (wq null: w[i]), wrapping.
+static void pair_sums_2d(const float *pts, int64_t n, const float *qry, int64_t nq, const float *a2, int32_t na,
+                         const float *b2, int32_t nb, int mode, int los, const float *period, const int64_t *w,
+                         const int64_t *wq, int64_t *out, int nthreads) {
   const vec3f *P = (const vec3f *)pts;
   const vec3f *Q = (const vec3f *)qry;
   if (na <= 0 || nb <= 0) return;
@@ -549,6 +550,7 @@ extern "C" void lsk_cpu_pair_counts_2d(const float *pts, int64_t n, const float 
   parallel_for(nq, nthreads, [&](int64_t b, int64_t e) {
     std::vector<uint64_t> cell(cells, 0);
     for (int64_t qi = b; qi < e; qi++) {
+      const uint64_t fq = wq ? (uint64_t)wq[qi] : 1;
       for (int64_t i = 0; i < n; i++) {
         float d[3] = {Q[qi].x - P[i].x, Q[qi].y - P[i].y, Q[qi].z - P[i].z};
         if (period)
@@ -562,7 +564,7 @@ extern "C" void lsk_cpu_pair_counts_2d(const float *pts, int64_t n, const float 
                               ? std::partition_point(b2, b2 + nb, [par2](float c) { return !(par2 < c); })
                               : std::partition_point(b2, b2 + nb, [par2, va](float c) { return !(par2 < c * va); });
         if (jb == b2 + nb) continue;
-        cell[(size_t)(ia - a2) * (size_t)nb + (size_t)(jb - b2)]++;
+        cell[(size_t)(ia - a2) * (size_t)nb + (size_t)(jb - b2)] += w ? fq * (uint64_t)w[i] : 1;
       }
     }
     std::lock_guard<std::mutex> lk(mu);
@@ -575,6 +577,22 @@ extern "C" void lsk_cpu_pair_counts_2d(const float *pts, int64_t n, const float 
       out[(size_t)i * nb + j] = (int64_t)(run + (i ? (uint64_t)out[(size_t)(i - 1) * nb + j] : 0));
     }
   }
+}
+
+extern "C" void lsk_cpu_pair_counts_2d(const float *pts, int64_t n, const float *qry, int64_t nq, const float *a2,
+                                       int32_t na, const float *b2, int32_t nb, int mode, int los,
+                                       const float *period, int64_t *out, int nthreads) {
+  pair_sums_2d(pts, n, qry, nq, a2, na, b2, nb, mode, los, period, nullptr, nullptr, out, nthreads);
+}
+
+// Weighted anisotropic pair sums: the brute force above with wq[q] * w[i] added to the pair's cell
+// in the place of 1 (wq null: all ones). Wrapping 64-bit sums and products: exact whenever the
+// true sums fit (the caller's check).
+extern "C" void lsk_cpu_weighted_pair_sums_2d(const float *pts, int64_t n, const float *qry, int64_t nq,
+                                              const float *a2, int32_t na, const float *b2, int32_t nb, int mode,
+                                              int los, const float *period, const int64_t *w, const int64_t *wq,
+                                              int64_t *out, int nthreads) {
+  pair_sums_2d(pts, n, qry, nq, a2, na, b2, nb, mode, los, period, w, wq, out, nthreads);
 }
 
 // lsk_cpu_kth_brute under a period: the k-th smallest pdist2 among those < cut2, else cut2.

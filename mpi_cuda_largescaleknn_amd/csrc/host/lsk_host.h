@@ -149,6 +149,12 @@ void lsk_cpu_weighted_profile(const float *pts, int64_t n, const float *qry, int
 void lsk_cpu_pair_counts_2d(const float *pts, int64_t n, const float *qry, int64_t nq, const float *a2, int32_t na,
                             const float *b2, int32_t nb, int mode, int los, const float *period, int64_t *out,
                             int nthreads);
+// The same with wq[q] * w[i] added per pair in the place of 1 (w: int64 [n]; wq: int64 [nq] or null
+// = all ones; negative allowed): the weighted anisotropic pair sums. Sums and products wrap in 64
+// bits: exact when (sum |w|) * (sum |wq|) < 2^63. With unit weights the counts above.
+void lsk_cpu_weighted_pair_sums_2d(const float *pts, int64_t n, const float *qry, int64_t nq, const float *a2,
+                                   int32_t na, const float *b2, int32_t nb, int mode, int los, const float *period,
+                                   const int64_t *w, const int64_t *wq, int64_t *out, int nthreads);
 // lsk_cpu_kth_brute / lsk_cpu_knn_brute under a period: brute force over all points with the
 // periodic squared distance above, the same selection (k-th smallest by bits among those <
 // cut2, else cut2) and the same tie rule (ascending (d² bits, row); unfilled: -1 / cut2).

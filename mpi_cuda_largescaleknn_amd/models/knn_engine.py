@@ -2093,6 +2093,126 @@ def weighted_pair_self_sums(points: torch.Tensor, radii, weights: torch.Tensor,
                                     squared=squared, period=period, stats=stats)
 
 
+# ---- weighted anisotropic pair sums: weights on DD(rp, pi) and DD(s, mu) (pair_counts_2d.hip)
+def _weighted_pairs2d(what: str, mode: str, index: LocalIndex, queries: torch.Tensor, first, second, weights,
+                      query_weights, los, squared: bool, period, stats: KnnStats | None) -> torch.Tensor:
+    a2, b2, los, per = _pairs2d_cutoffs(what, mode, first, second, los, squared, period)
+    if index.qrot is not None or index.line:
+        raise ValueError(f"{what}: an index built in a rotated frame or sorted by line keys is not supported")
+    queries = _check_foreign(what, index, queries)
+    nq, n = queries.shape[0], index.n
+    pw = _point_weights(what, index, weights)
+    wq = None
+    if query_weights is not None:
+        wq = K.int64_weights(what, "query_weights", query_weights, nq, index.device)
+    check_pair_sum_bound(what, pw, wq, nq)
+    if nq == 0 or n == 0:
+        return torch.zeros((a2.shape[0], b2.shape[0]), dtype=torch.int64, device=index.device)
+    if not K.is_gpu(index.pts):
+        KERNELS_USED.add("cpu")
+        return K.weighted_pair_sums_2d_cpu(index.pts[:n], queries, a2, b2, pw.sorted, mode, los, per,
+                                           query_weights=wq)
+    qsorted, qperm = prepare_queries(index, queries, locate=False)[:2]
+    names = _RADIUS_STATS if per is None else _RADIUS_PERIODIC_STATS
+    raw = torch.zeros(len(names), dtype=torch.int64, device=index.device) if stats is not None else None
+    out = K.weighted_pair_sums_2d_gpu(index.tree(), qsorted, nq, a2, b2, mode, los, qperm, pw.sorted, pw.prefix,
+                                      period=per, query_weights=wq, stats=raw)
+    KERNELS_USED.add("weighted_pair_sums_2d")
+    if stats is not None:
+        for nm, v in zip(names, raw.cpu().tolist()):
+            stats.counters[nm] = stats.counters.get(nm, 0) + int(v)
+    return out
+
+
+def _weighted_pairs2d_points(what: str, mode: str, points: torch.Tensor, queries: torch.Tensor, first, second,
+                             weights, query_weights, los, squared: bool, period,
+                             stats: KnnStats | None) -> torch.Tensor:
+    """The *_query_* / *_self_* forms: an index built once from `points` (the arguments are checked
+    all the same when there is nothing to index)."""
+    index, empty = _pairs2d_index(what, mode, points, queries, first, second, los, squared, period)
+    if index is None:
+        K.int64_weights(what, "weights", weights, 0, points.device)
+        if query_weights is not None:
+            K.int64_weights(what, "query_weights", query_weights, queries.shape[0], queries.device)
+        return empty
+    return _weighted_pairs2d(what, mode, index, queries, first, second, weights, query_weights, los, squared,
+                             period, stats)
+
+
+def weighted_pair_sums_rppi(index: LocalIndex, queries: torch.Tensor, rp, pi, weights, query_weights=None, los=2,
+                            squared: bool = False, period=None, stats: KnnStats | None = None) -> torch.Tensor:
+    """int64 [Bp, Bl] on the index's device: WS[i, j] = the sum of query_weights[q] * weights[p]
+    over the pairs (query q, indexed point p) with perp2 < cut2_of(rp[i]) and par2 < cut2_of(pi[j]),
+    strict and cumulative on both axes: pair_counts_rppi with a weight per point and per query in
+    the place of 1, from the same walk of the tree (with unit weights it equals pair_counts_rppi bit
+    for bit, and the two walks' radius_* counters are equal). shell_counts_2d(WS) is the binned
+    weighted DD(rp, pi); weights +1 on a data set and -alpha on its randoms give (D - R)(D - R).
+
+    weights: int64 [n] on the index's device, one per row of the indexed array, negative allowed,
+    or the PointWeights of prepare_point_weights; query_weights: int64 [nq] on the index's device
+    or None (all ones). The sums are exact and equal the brute-force oracle bit for bit: max|w| * n
+    must be below 2^62 and (sum |weights|) * (sum |query_weights|) (nq without query weights) below
+    2^63, both checked on the host before any kernel runs; the device then adds and multiplies in
+    wrapping 64-bit arithmetic in any order, and two runs give the same bits. Float masses become
+    such weights with fixed_point_weights. rp, pi, los, squared, period, the slices of 2048 cells
+    and the limit on NaN indexed points as for pair_counts_rppi; a query with a NaN or infinite
+    coordinate adds nothing. Weights of another dtype, shape or device, weights prepared for
+    another index, either bound exceeded and every argument error of pair_counts_rppi raise
+    ValueError; an index built in a rotated frame or sorted by line keys is not supported. `stats`
+    receives the radius_* counters."""
+    return _weighted_pairs2d("weighted_pair_sums_rppi", "rppi", index, queries, rp, pi, weights, query_weights, los,
+                             squared, period, stats)
+
+
+def weighted_pair_query_sums_rppi(points: torch.Tensor, queries: torch.Tensor, rp, pi, weights: torch.Tensor,
+                                  query_weights: torch.Tensor | None = None, los=2, squared: bool = False,
+                                  period=None, stats: KnnStats | None = None) -> torch.Tensor:
+    """weighted_pair_sums_rppi over an index built once from `points`, in the points' own frame."""
+    return _weighted_pairs2d_points("weighted_pair_query_sums_rppi", "rppi", points, queries, rp, pi, weights,
+                                    query_weights, los, squared, period, stats)
+
+
+def weighted_pair_self_sums_rppi(points: torch.Tensor, rp, pi, weights: torch.Tensor,
+                                 query_weights: torch.Tensor | None = None, los=2, squared: bool = False,
+                                 period=None, stats: KnnStats | None = None) -> torch.Tensor:
+    """weighted_pair_query_sums_rppi with the points as their own queries and, unless query_weights
+    is given, `weights` on both sides: ordered pairs, (p, q) and (q, p) both, and every finite point
+    with itself (perp2 = par2 = 0: w[p]^2 in every cell with cutoffs > 0), like
+    weighted_pair_self_sums."""
+    return _weighted_pairs2d_points("weighted_pair_self_sums_rppi", "rppi", points, points, rp, pi, weights,
+                                    weights if query_weights is None else query_weights, los, squared, period,
+                                    stats)
+
+
+def weighted_pair_sums_smu(index: LocalIndex, queries: torch.Tensor, s, mu, weights, query_weights=None, los=2,
+                           squared: bool = False, period=None, stats: KnnStats | None = None) -> torch.Tensor:
+    """int64 [Bs, Bm] on the index's device: WS[i, j] = the sum of query_weights[q] * weights[p]
+    over the pairs with d2 < cut2_of(s[i]) and par2 < mu2[j] * d2: pair_counts_smu with weights, as
+    weighted_pair_sums_rppi is pair_counts_rppi with weights. A pair with d2 == 0 adds to no cell;
+    there is no whole-box acceptance in this mode. s, mu and everything else as for
+    pair_counts_smu, weights and errors as for weighted_pair_sums_rppi."""
+    return _weighted_pairs2d("weighted_pair_sums_smu", "smu", index, queries, s, mu, weights, query_weights, los,
+                             squared, period, stats)
+
+
+def weighted_pair_query_sums_smu(points: torch.Tensor, queries: torch.Tensor, s, mu, weights: torch.Tensor,
+                                 query_weights: torch.Tensor | None = None, los=2, squared: bool = False,
+                                 period=None, stats: KnnStats | None = None) -> torch.Tensor:
+    """weighted_pair_sums_smu over an index built once from `points`, in the points' own frame."""
+    return _weighted_pairs2d_points("weighted_pair_query_sums_smu", "smu", points, queries, s, mu, weights,
+                                    query_weights, los, squared, period, stats)
+
+
+def weighted_pair_self_sums_smu(points: torch.Tensor, s, mu, weights: torch.Tensor,
+                                query_weights: torch.Tensor | None = None, los=2, squared: bool = False,
+                                period=None, stats: KnnStats | None = None) -> torch.Tensor:
+    """weighted_pair_query_sums_smu with the points as their own queries and, unless query_weights is
+    given, `weights` on both sides: ordered pairs; a point with itself (d2 == 0) adds nowhere."""
+    return _weighted_pairs2d_points("weighted_pair_self_sums_smu", "smu", points, points, s, mu, weights,
+                                    weights if query_weights is None else query_weights, los, squared, period,
+                                    stats)
+
+
 def fixed_point_weights(weights: torch.Tensor, n_terms: int | None = None, bits: int = 62) -> tuple:
     """(int64 tensor, s): float32 / float64 weights (masses) as exact fixed-point integers w_fix =
     rint(w * 2^-s), for the weighted_* functions; the physical value of a result is result * 2^s.

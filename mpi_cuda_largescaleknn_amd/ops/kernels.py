@@ -1406,6 +1406,58 @@ def weighted_pair_sums_gpu(tree: tuple, qsorted: torch.Tensor, nq: int, cut2s, o
                            weights=(wsorted, wpre), query_weights=query_weights)
 
 
+def weighted_pair_sums_2d_cpu(points: torch.Tensor, queries: torch.Tensor, a2, b2, weights: torch.Tensor, mode: str,
+                              los: int = 2, period=None, query_weights: torch.Tensor | None = None) -> torch.Tensor:
+    """CPU oracle (brute force over all pairs) of the weighted anisotropic pair sums: int64 [Ba, Bb],
+    cumulative on both axes, pair_counts_2d_cpu with query_weights[q] * weights[p] added per pair in
+    the place of 1. weights: int64 [n], one per row of `points`; query_weights: int64 [nq] or None
+    (all ones); negative allowed. Sums and products wrap in 64 bits (exact when (sum |w|) * (sum
+    |wq|) < 2^63). With unit weights this is pair_counts_2d_cpu."""
+    what = "weighted_pair_sums_2d_cpu"
+    a, b = _pairs2d_args(what, a2, b2, mode, los)
+    per = None if period is None else check_period(what, period)
+    pts = points.contiguous().float().cpu()
+    q = queries.contiguous().float().cpu()
+    w = int64_weights(what, "weights", weights, pts.shape[0]).cpu()
+    wq = None if query_weights is None else int64_weights(what, "query_weights", query_weights, q.shape[0]).cpu()
+    out = torch.zeros((a.shape[0], b.shape[0]), dtype=torch.int64)
+    _native.host().lsk_cpu_weighted_pair_sums_2d(_ptr(pts), pts.shape[0], _ptr(q), q.shape[0], _ptr(a), a.shape[0],
+                                                 _ptr(b), b.shape[0], PAIRS2D_MODES[mode], int(los),
+                                                 None if per is None else _period_c(per), _ptr(w), _ptr(wq),
+                                                 _ptr(out), _nthreads())
+    return out
+
+
+def weighted_pair_sums_2d_gpu(tree: tuple, qsorted: torch.Tensor, nq: int, a2, b2, mode: str, los: int,
+                              out_perm: torch.Tensor, wsorted: torch.Tensor, wprefix: torch.Tensor,
+                              period: tuple[float, float, float] | None = None,
+                              query_weights: torch.Tensor | None = None,
+                              stats: torch.Tensor | None = None) -> torch.Tensor:
+    """The weighted anisotropic pair sums (pair_counts_2d.hip, the weight policy) on the current
+    stream: int64 [Ba, Bb] on the tree's device, what weighted_pair_sums_2d_cpu defines, from the
+    walk of pair_counts_2d_gpu. wsorted / wprefix: int64 [n] / [n + 1], the weights in the tree's
+    curve order and their exclusive prefix sum; query_weights: int64 [nq] in query order or None.
+    The caller guarantees max|w| * n < 2^62 and (sum |w|) * (sum |query_weights|) < 2^63.
+    Everything else as for pair_counts_2d_gpu."""
+    what = "weighted_pair_sums_2d_gpu"
+    a, b = _pairs2d_args(what, a2, b2, mode, los)
+    tv = _walk_view(what, tree, qsorted, nq, out_perm)
+    dev = tree[0].device
+    _profile_stats(what, stats, period, dev)
+    _weighted_args(what, tree, wsorted, wprefix)
+    wq = query_weights
+    if wq is not None and (wq.dtype != torch.int64 or wq.dim() != 1 or wq.shape[0] != nq or not wq.is_contiguous()
+                           or wq.device != dev):
+        raise ValueError(f"{what}: query_weights must be a contiguous int64 [{nq}] tensor on the tree's device")
+    res = torch.empty((a.shape[0], b.shape[0]), dtype=torch.int64, device=dev)
+    adev, bdev = a.to(dev), b.to(dev)
+    check(_native.hip().lsk_hip_weighted_pair_sums_2d(
+        C.byref(tv), _ptr(qsorted), int(nq), _ptr(adev), a.shape[0], _ptr(bdev), b.shape[0], PAIRS2D_MODES[mode],
+        int(los), None if period is None else _period_c(period), _ptr(out_perm), _ptr(wsorted), _ptr(wprefix),
+        _ptr(wq), _ptr(res), _ptr(stats), _stream(tree[0])), "weighted_pair_sums_2d")
+    return res
+
+
 # --------------------------------------------------------------------------- periodic k-NN
 def kth_periodic_cpu(points: torch.Tensor, queries: torch.Tensor, k: int, cut2: float, period) -> torch.Tensor:
     """CPU oracle (brute force): kth_cpu with the periodic squared distance of

@@ -7,7 +7,7 @@
     python scripts/radius_bench.py --profile B [-r R] [--self-queries] [--points ..] [--queries ..] [--mean ..]
                                    [--steps ..] [--warmup ..] [--period ..] [--weights]
     python scripts/radius_bench.py --pairs-2d BPxBL [--smu] [-r R] [--self-queries] [--points ..] [--queries ..]
-                                   [--steps ..] [--warmup ..] [--period ..] [--skip-pair-list]
+                                   [--steps ..] [--warmup ..] [--period ..] [--skip-pair-list] [--weights]
 
 Uniform points in the unit cube and uniform queries from another seed; the radius is the one
 whose ball holds --mean points at the data's density (queries near the faces see fewer, so
@@ -55,6 +55,16 @@ route without the kernel: radius_neighbors(sort=False) at the enclosing radius i
 respect max_pairs, the differences re-derived and binned in torch (its cells are compared with the
 kernel's and the number that differ is reported: torch promises no fma). The JSON carries the
 medians and the radius_* counters of the two walks.
+
+--pairs-2d BPxBL --weights: the weighted anisotropic pair sums beside them. int64 weights drawn from
++-2^15 on the points and +-2^2 on the queries (prepared once, outside the timed region); one
+weighted_pair_sums_rppi (_smu) call is timed alternately with the cases above, and the pair-list
+route bins wq * w (an integer index_add) in the place of 1. The radius_* counters of the weighted
+and the unweighted walk must be equal (asserted). Before anything is printed the weighted cells
+are compared with one more, untimed pass of the pair-list route that forms perp2 and d2 as the
+kernel does (the square exact in float64, one sum, rounded to float32: the fma but for a double
+rounding that needs a 29-bit coincidence): every cell must be equal, or the run fails. The timed
+route's own float32 cells are reported as before (the number that differ).
 """
 from __future__ import annotations
 
@@ -196,8 +206,11 @@ def weighted_bench(a, p: torch.Tensor, q: torch.Tensor, r: float, per: dict) -> 
     return 0 if same_list and same_sums else 1
 
 
-def pair_list_cells(index, p, q, R, first2, second2, smu: bool, per: dict, period, chunk: int) -> torch.Tensor:
-    """The differential [B1, B2] cells (int64) by way of the pair lists at the enclosing radius R."""
+def pair_list_cells(index, p, q, R, first2, second2, smu: bool, per: dict, period, chunk: int,
+                    weights: tuple | None = None, exact: bool = False) -> torch.Tensor:
+    """The differential [B1, B2] cells (int64) by way of the pair lists at the enclosing radius R;
+    weights = (w, wq): every pair adds wq[q] * w[p] in the place of 1; exact: perp2 and d2 as the
+    float32 fma of the kernel, by way of float64."""
     b1, b2 = first2.shape[0], second2.shape[0]
     cells = torch.zeros(b1 * b2, dtype=torch.int64, device=q.device)
     for a in range(0, q.shape[0], chunk):
@@ -212,16 +225,22 @@ def pair_list_cells(index, p, q, R, first2, second2, smu: bool, per: dict, perio
                     x = d[:, ax]
                     d[:, ax] = torch.where(x > 0.5 * L, x - L, torch.where(x < -0.5 * L, x + L, x))
         par2 = d[:, 2] * d[:, 2]
-        perp2 = torch.addcmul(d[:, 0] * d[:, 0], d[:, 1], d[:, 1])
+        if exact:
+            perp2 = (d[:, 1].double() * d[:, 1].double() + (d[:, 0] * d[:, 0]).double()).float()
+        else:
+            perp2 = torch.addcmul(d[:, 0] * d[:, 0], d[:, 1], d[:, 1])
         if smu:
-            d2 = perp2 + par2
+            d2 = (d[:, 2].double() * d[:, 2].double() + perp2.double()).float() if exact else perp2 + par2
             i0 = torch.bucketize(d2, first2, right=True)
             j0 = b2 - (par2[:, None] < second2[None, :] * d2[:, None]).sum(1)
         else:
             i0 = torch.bucketize(perp2, first2, right=True)
             j0 = torch.bucketize(par2, second2, right=True)
         ok = (i0 < b1) & (j0 < b2)
-        cells += torch.bincount((i0 * b2 + j0)[ok], minlength=b1 * b2)
+        if weights is None:
+            cells += torch.bincount((i0 * b2 + j0)[ok], minlength=b1 * b2)
+        else:
+            cells.index_add_(0, (i0 * b2 + j0)[ok], (weights[1][rows] * weights[0][idx.long()])[ok])
     return cells.view(b1, b2)
 
 
@@ -244,9 +263,19 @@ def pairs2d_bench(a, p: torch.Tensor, q: torch.Tensor, per: dict) -> int:
         "pairs1d": lambda **kw: out.__setitem__(
             "pairs1d", E.pair_counts(index, q, [Renc * (i + 1) / b1 for i in range(b1)], **per, **kw)),
     }
+    wts = None
+    if a.weights:
+        g = torch.Generator(device=p.device).manual_seed(5)
+        w = torch.randint(-(1 << 15), (1 << 15) + 1, (p.shape[0],), dtype=torch.int64, device=p.device, generator=g)
+        wq = torch.randint(-4, 5, (q.shape[0],), dtype=torch.int64, device=p.device, generator=g)
+        wts = (w, wq)
+        pw = E.prepare_point_weights(index, w)
+        wfn2d = E.weighted_pair_sums_smu if a.smu else E.weighted_pair_sums_rppi
+        cases["wpairs2d"] = lambda **kw: out.__setitem__(
+            "wpairs2d", wfn2d(index, q, first, second, pw, query_weights=wq, **per, **kw))
     if not a.skip_pair_list:
         cases["pair_list"] = lambda: out.__setitem__(
-            "list", pair_list_cells(index, p, q, Renc, first2, second2, a.smu, per, a.period, chunk))
+            "list", pair_list_cells(index, p, q, Renc, first2, second2, a.smu, per, a.period, chunk, wts))
     times = {name: [] for name in cases}
     for step in range(a.warmup + a.steps):
         for name, fn in cases.items():
@@ -276,14 +305,30 @@ def pairs2d_bench(a, p: torch.Tensor, q: torch.Tensor, per: dict) -> int:
         "pairs2d_s": med["pairs2d"], "pairs1d_s": med["pairs1d"], "pair_list_s": med.get("pair_list"),
         "spread": {name: [min(ts), max(ts)] for name, ts in times.items()}, "counters": counters,
     }
+    ok = True
+    if a.weights:
+        assert counters["wpairs2d"] == counters["pairs2d"], (counters["wpairs2d"], counters["pairs2d"])
+        rec.update({"weights": "int64 +-2^15, query weights +-2^2", "wpairs2d_s": med["wpairs2d"],
+                    "weighted_over_pairs2d": med["wpairs2d"] / med["pairs2d"], "counters_equal": True,
+                    "weighted_total": int(out["wpairs2d"][-1, -1])})
+        if "pair_list" in med:
+            rec["pair_list_over_weighted"] = med["pair_list"] / med["wpairs2d"]
     if "list" in out:
+        counted = out["list"] if wts is None else \
+            pair_list_cells(index, p, q, Renc, first2, second2, a.smu, per, a.period, chunk)
+        moved = E.shell_counts_2d(S) != counted
         rec["pair_list_chunk"] = chunk
-        rec["pair_list_cells_differing"] = int((E.shell_counts_2d(S) != out["list"]).sum())
-        rec["pair_list_total"] = int(out["list"].sum())
+        rec["pair_list_cells_differing"] = int(moved.sum())
+        rec["pair_list_total"] = int(counted.sum())
+        if wts is not None:
+            rec["weighted_pair_list_cells_differing"] = int((E.shell_counts_2d(out["wpairs2d"]) != out["list"]).sum())
+            fma = pair_list_cells(index, p, q, Renc, first2, second2, a.smu, per, a.period, chunk, wts, exact=True)
+            ok = bool(torch.equal(E.shell_counts_2d(out["wpairs2d"]), fma))
+            rec["weighted_equals_pair_list"] = ok
     if a.period is not None:
         rec["period"] = list(a.period)
     print(json.dumps(rec), flush=True)
-    return 0
+    return 0 if ok else 1
 
 
 def main() -> int:
@@ -299,7 +344,8 @@ def main() -> int:
     ap.add_argument("--profile", type=int, default=0, metavar="B", help="time the radius profile at B radii instead")
     ap.add_argument("-r", dest="radius", type=float, default=None, help="--profile: the largest radius")
     ap.add_argument("--self-queries", action="store_true", help="--profile: the points are their own queries")
-    ap.add_argument("--weights", action="store_true", help="--profile: the weighted profile and its alternatives")
+    ap.add_argument("--weights", action="store_true",
+                    help="--profile: the weighted profile and its alternatives; --pairs-2d: the weighted sums too")
     ap.add_argument("--pairs-2d", default=None, metavar="BPxBL", help="time the anisotropic pair counts instead")
     ap.add_argument("--smu", action="store_true", help="--pairs-2d: the (s, mu) mode")
     ap.add_argument("--skip-pair-list", action="store_true", help="--pairs-2d: without the pair-list route")
