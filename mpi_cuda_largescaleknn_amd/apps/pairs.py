@@ -1,8 +1,9 @@
 """hipKNN_pairs — anisotropic pair counts along a line of sight: DD(rp, pi) and DD(s, mu).
 
     hipKNN_pairs <points.float3> <queries.float3> (--rp R1,R2,... --pi P1,P2,... | --s S1,S2,... --mu M1,M2,...)
-                 [--los x|y|z] [--squared] [--period L | Lx,Ly,Lz] [--weights W.i64 [--query-weights WQ.i64]]
-                 [--chunk N] [--device auto|cuda|cpu] [--stats f.json] [-v] -o <PREFIX>
+                 [--los x|y|z|midpoint [--observer ox,oy,oz]] [--squared] [--period L | Lx,Ly,Lz]
+                 [--weights W.i64 [--query-weights WQ.i64]] [--chunk N] [--device auto|cuda|cpu] [--stats f.json]
+                 [-v] -o <PREFIX>
 
 For every pair (row of the query file, row of the point file) the float32 differences q - p, with
 --period their minimum image, are split along the line of sight --los (a box axis, default z):
@@ -15,6 +16,13 @@ out the pairs exactly along the line of sight, which mu = inf takes in. --square
 --s hold the squared cutoffs themselves (--mu is always plain mu). With --period a radius along
 the line of sight may not exceed half the period of that axis, one across it not half the period
 of a finite perpendicular axis.
+
+--los midpoint: every pair has its own line of sight, the direction from --observer (three finite
+numbers, default 0,0,0) to the pair's midpoint, as for survey catalogues, light cones and mocks
+with randoms. With l = (q - o) + (p - o) per axis and sl = fmaf(dz, lz, fmaf(dy, ly, dx * lx)):
+par2 = (sl / dist2(l)) * sl and perp2 = d2 - par2 (a negative one becomes 0), all float32; the
+cells are the same. A pair whose midpoint is the observer counts nowhere. Open box only: --period
+is refused, and so is --observer with an axis --los.
 
 PREFIX.pairs2d holds the counts, headerless int64 [B1][B2], row-major. One line per row of cells
 is printed: the first-axis edge, then the row's binned (not cumulative) counts. The index over the
@@ -55,7 +63,7 @@ def edges_arg(name: str):
 
 
 def add_pairs_options(ap: argparse.ArgumentParser) -> None:
-    """--rp --pi | --s --mu, --los, --squared and --period (also lsknn_tools pcheck)."""
+    """--rp --pi | --s --mu, --los, --observer, --squared and --period (also lsknn_tools pcheck)."""
     ap.add_argument("--rp", type=edges_arg("--rp"), default=None, metavar="R1,R2,...",
                     help="ascending radii across the line of sight (with --pi)")
     ap.add_argument("--pi", type=edges_arg("--pi"), default=None, metavar="P1,P2,...",
@@ -64,7 +72,10 @@ def add_pairs_options(ap: argparse.ArgumentParser) -> None:
                     help="ascending separations (with --mu)")
     ap.add_argument("--mu", type=edges_arg("--mu"), default=None, metavar="M1,M2,...",
                     help="ascending cosines to the line of sight, inf allowed (with --s)")
-    ap.add_argument("--los", choices=["x", "y", "z"], default="z", help="the line-of-sight axis (default z)")
+    ap.add_argument("--los", type=str.lower, choices=["x", "y", "z", "midpoint"], default="z",
+                    help="the line-of-sight axis (default z), or midpoint: from --observer to each pair's midpoint")
+    ap.add_argument("--observer", type=edges_arg("--observer"), default=None, metavar="ox,oy,oz",
+                    help="with --los midpoint: the observer, default 0,0,0 (a negative first value: --observer=-1,0,0)")
     ap.add_argument("--squared", action="store_true", help="--rp / --pi / --s are squared cutoffs")
     add_period_option(ap)
     ap.add_argument("--weights", default=None, metavar="W.i64",
@@ -108,11 +119,13 @@ def main(argv: list[str] | None = None) -> int:
         sys.stderr.write("hipKNN_pairs: runs as one process on one device\n")
         return 1
     try:  # before anything is read or written
-        E._pairs2d_cutoffs("hipKNN_pairs", a.mode, a.first, a.second, a.los, a.squared, a.period)
+        E._pairs2d_cutoffs("hipKNN_pairs", a.mode, a.first, a.second, a.los, a.squared, a.period, a.observer)
     except ValueError as e:
         sys.stderr.write(f"hipKNN_pairs: {e}\n")
         return 1
     per = {} if a.period is None else {"period": a.period}
+    if a.observer is not None:
+        per["observer"] = a.observer
     dev = _device(a.device)
     gpu = dev.type == "cuda"
     stats = E.KnnStats() if a.stats else None
@@ -168,6 +181,8 @@ def main(argv: list[str] | None = None) -> int:
             rec["squared"] = True
         if a.period is not None:
             rec["period"] = list(a.period)
+        if a.observer is not None:
+            rec["observer"] = list(a.observer)
         with open(a.stats, "w") as f:
             json.dump(rec, f, indent=1)
     return 0

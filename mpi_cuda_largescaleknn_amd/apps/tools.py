@@ -23,7 +23,8 @@
            -> hipKNN_radius --profile --weights' PREFIX.wprofile and PREFIX.wpairs against the oracle, on
               the same sampling rules
     python -m mpi_cuda_largescaleknn_amd.apps.tools pcheck in.float3 q.float3 PREFIX (--rp .. --pi .. | --s .. --mu ..)
-           [--los x|y|z] [--squared] [--period L | Lx,Ly,Lz] [--weights W.i64 [--query-weights WQ.i64]]
+           [--los x|y|z|midpoint [--observer ox,oy,oz]] [--squared] [--period L | Lx,Ly,Lz]
+           [--weights W.i64 [--query-weights WQ.i64]]
            -> hipKNN_pairs' PREFIX.pairs2d (--weights: PREFIX.wpairs2d) against the brute-force oracle,
               every cell (at most 65536 queries: the oracle visits every pair)
     python -m mpi_cuda_largescaleknn_amd.apps.tools fixweights in.float out.i64 [--bits N] [--terms T]
@@ -199,7 +200,8 @@ def pcheck(a) -> int:
     """PREFIX.pairs2d (--weights: PREFIX.wpairs2d) of hipKNN_pairs against the oracle, every cell."""
     from ..models.knn_engine import _pairs2d_cutoffs
     try:
-        a2, b2, los, per = _pairs2d_cutoffs("pcheck", a.mode, a.first, a.second, a.los, a.squared, a.period)
+        a2, b2, los, per = _pairs2d_cutoffs("pcheck", a.mode, a.first, a.second, a.los, a.squared, a.period,
+                                            a.observer)
     except ValueError as e:
         print(e)
         return 1
@@ -224,7 +226,10 @@ def pcheck(a) -> int:
         print(f"size mismatch: {got.shape[0]} cells for {a2.shape[0]} x {b2.shape[0]} edges")
         return 1
     got = got.view(a2.shape[0], b2.shape[0])
-    if weighted:
+    if isinstance(los, tuple):  # --los midpoint: the observer
+        ref = K.weighted_pair_sums_2d_observer_cpu(pts, qry, a2, b2, w, a.mode, los, query_weights=wq) if weighted \
+            else K.pair_counts_2d_observer_cpu(pts, qry, a2, b2, a.mode, los)
+    elif weighted:
         ref = K.weighted_pair_sums_2d_cpu(pts, qry, a2, b2, w, a.mode, los, per, query_weights=wq)
     else:
         ref = K.pair_counts_2d_cpu(pts, qry, a2, b2, a.mode, los, per)

@@ -101,7 +101,38 @@
 // max|w| * n < 2^62 and (sum |w|) * (sum |wq|) < 2^63, every cell, partial sum and cumulative
 // entry is a sum of wq * w over a subset of the pairs, so wrapping 64-bit arithmetic in any order
 // gives the true value, and two runs give the same bits.
+//
+// Observer line of sight (lsk_hip_pair_counts_2d_observer, lsk_hip_weighted_pair_sums_2d_observer;
+// kObserver, open box only). Every pair has its own line of sight, the direction from an observer
+// o (three finite floats) to the pair's midpoint. Per pair, in float32 without contraction:
+//     dx = q.x - p.x, dy, dz likewise            (the open-box difference above)
+//     lx = (q.x - o.x) + (p.x - o.x), ly, lz     (twice the vector observer -> midpoint)
+//     sl = fmaf(dz, lz, fmaf(dy, ly, dx * lx))
+//     ll = dist2(lx, ly, lz),  d2 = dist2(dx, dy, dz)
+//     par2  = (sl / ll) * sl                     (one correctly rounded division, one product)
+//     perp2 = d2 - par2;  if (perp2 < 0) perp2 = 0     (a NaN stays a NaN)
+// and the cells are those above: perp2 < cp2[i] and par2 < cl2[j], or d2 < cs2[i] and par2 <
+// mu2[j] * d2. sl / ll has no dimension, so par2 is a squared length and the usable range of
+// coordinates is that of d2. Swapping q and p negates sl exactly and leaves ll and d2 alone:
+// every quantity is symmetric in its bits. A pair whose midpoint is the observer (ll == 0) has a
+// NaN or infinite par2 and counts nowhere; a point with itself has par2 = perp2 = 0 (every (rp,
+// pi) cell with cutoffs > 0, no (s, mu) cell); par2 may exceed d2 by rounding (perp2 clamps to 0;
+// an edge mu = 1 excludes such a pair, inf takes it in). The difference functor ObsDiff is a
+// sibling of LosDiff with q - o hoisted out of the candidate loop; row and column search, cell
+// update, slices, end of block and cumulate are the ones above.
+// Cull, observer mode. There is no axis: the cull is the ball box distance² < cull2 in both modes
+// (box_box_dist2 / box_dist2, each <= the float d2 of every pair of the box, the proof of
+// box_dist2). (s, mu): cull2 = cs2[r1 - 1]. (rp, pi): a pair that counts in the slice has
+// fl(d2 - par2) < A (or that difference < 0 <= A) and par2 < B, with A = cp2[r1 - 1] and B =
+// cl2[nb - 1]. Rounding to nearest is monotone and A is a float, so fl(x) < A implies x < A: the
+// real d2 - par2 < A, and with par2 < B the float d2 < A + B as a real number. The host passes
+// cull2 = nextafterf((float)((double)A + (double)B), +inf) >= A + B (the double sum of two floats
+// is within one rounding of the real one, the float after its float rounding is above both), inf
+// when either cutoff is: a node's box distance² <= d2 < cull2 for every pair that counts, so the
+// cull drops none. There is no whole-box acceptance: neither component is monotone per axis under
+// a per-pair direction (the argument given for mu above), the accept counter stays 0.
 #include <algorithm>
+#include <cmath>
 
 #include "periodic_image.h"
 
@@ -135,6 +166,21 @@ struct WeightedPair2dArgs : Pair2dArgs {
   const int64_t *wsorted;  // [n] point weights in curve order
   const int64_t *wpre;     // [n + 1] exclusive prefix sum of wsorted
   const int64_t *wq;       // optional [nq] query weights, query order
+};
+
+// kObserver: the policy's arguments and the observer's.
+template <class Base>
+struct ObserverArgs : Base {
+  float o[3];   // the observer
+  float cull2;  // the slice's ball: a node is kept iff its box distance² < cull2
+};
+template <class Policy, bool kObserver>
+struct WalkArgs {
+  typedef typename Policy::args type;
+};
+template <class Policy>
+struct WalkArgs<Policy, true> {
+  typedef ObserverArgs<typename Policy::args> type;
 };
 
 // What a pair adds to its cell. args: the kernel's argument block; column: what travels with a
@@ -197,6 +243,27 @@ struct LosDiff {
   }
 };
 
+// Its sibling for the observer line of sight (open box): the header's arithmetic, literally. qo =
+// q - o is the lane's own, computed once before the walk.
+struct ObsDiff {
+  float ox, oy, oz;
+  float qox, qoy, qoz;
+  float &par2, &perp2;
+  __device__ __forceinline__ float operator()(const lsk::GroupQuery &Q, float x, float y, float z,
+                                              bool &mine) const {
+    const float dx = Q.x - x, dy = Q.y - y, dz = Q.z - z;
+    mine = true;
+    const float lx = qox + (x - ox), ly = qoy + (y - oy), lz = qoz + (z - oz);
+    const float sl = fmaf(dz, lz, fmaf(dy, ly, dx * lx));
+    const float ll = lsk::dist2(lx, ly, lz);
+    const float d2 = lsk::dist2(dx, dy, dz);
+    par2 = __fdiv_rn(sl, ll) * sl;
+    const float pp = d2 - par2;
+    perp2 = pp < 0.f ? 0.f : pp;  // (a select, not fmaxf: a NaN stays a NaN)
+    return d2;
+  }
+};
+
 // The first index in [0, m) whose test holds, given that test(m - 1) holds and that the tests
 // ascend (false ... false true ... true). `steps` = ceil(log2(m)), uniform.
 template <class Test>
@@ -221,9 +288,12 @@ __device__ __forceinline__ float open_far(float q, float lo, float hi) {
   return fmaxf(fabsf(lo - q), fabsf(hi - q));
 }
 
-// kSmu: (s, mu) mode, else (rp, pi).
-template <bool kPeriodic, bool kSmu, class Policy>
-__global__ __launch_bounds__(kWaves * 64) void pair_counts_2d_walk_kernel(const typename Policy::args A) {
+// kSmu: (s, mu) mode, else (rp, pi). kObserver: the per-pair line of sight of an observer (open
+// box), else the axis A.los.
+template <bool kPeriodic, bool kSmu, class Policy, bool kObserver = false>
+__global__ __launch_bounds__(kWaves * 64) void pair_counts_2d_walk_kernel(
+    const typename WalkArgs<Policy, kObserver>::type A) {
+  static_assert(!(kPeriodic && kObserver), "a periodic box has no observer");
   __shared__ uint32_t stk_all[kWaves][lsk::kWalkStack];
   __shared__ u64 cells[kCells];
   __shared__ float ca[kMaxEdges + 1];  // the slice's first-axis cutoffs, after the one below it
@@ -309,7 +379,20 @@ __global__ __launch_bounds__(kWaves * 64) void pair_counts_2d_walk_kernel(const 
 
   if (active && __ballot(live)) {
     const lsk::box3f gb = lsk::group_box(Q, live);
-    if (!kPeriodic) {
+    if constexpr (kObserver) {
+      const lsk::vec3f q{Q.x, Q.y, Q.z};
+      const float cull2 = A.cull2;
+      const ObsDiff diff{A.o[0], A.o[1], A.o[2], Q.x - A.o[0], Q.y - A.o[1], Q.z - A.o[2], par2, perp2};
+      lsk::ball_walk<true>(
+          T, stk_all[wid], lane,
+          [&](const float4 &lo4, const float4 &hi4) { return lsk::box_box_dist2(gb, lsk::box_of(lo4, hi4)) < cull2; },
+          [&](uint32_t, int32_t, uint32_t sp, const float4 &lo4, const float4 &hi4) {
+            s_nodes++;
+            cov.pop(sp);
+            return live && lsk::box_dist2(q, {lo4.x, lo4.y, lo4.z}, {hi4.x, hi4.y, hi4.z}) < cull2;
+          },
+          [&](uint32_t node, bool use) { scan(node, use, diff); });
+    } else if (!kPeriodic) {
       const lsk::vec3f q{Q.x, Q.y, Q.z};
       // (rp, pi): the two gap² of a query range against a box, both below their cutoffs
       auto near_ok = [&](float qlx, float qhx, float qly, float qhy, float qlz, float qhz, const float4 &lo4,
@@ -420,21 +503,24 @@ __global__ __launch_bounds__(kCumThreads) void pair_counts_2d_cumulate_kernel(u6
   }
 }
 
-template <bool kPeriodic, class Policy>
-void launch_walk(const typename Policy::args &A, bool smu, unsigned blocks, hipStream_t st) {
+template <bool kPeriodic, class Policy, bool kObserver = false>
+void launch_walk(const typename WalkArgs<Policy, kObserver>::type &A, bool smu, unsigned blocks, hipStream_t st) {
   if (smu)
-    pair_counts_2d_walk_kernel<kPeriodic, true, Policy><<<blocks, kWaves * 64, 0, st>>>(A);
+    pair_counts_2d_walk_kernel<kPeriodic, true, Policy, kObserver><<<blocks, kWaves * 64, 0, st>>>(A);
   else
-    pair_counts_2d_walk_kernel<kPeriodic, false, Policy><<<blocks, kWaves * 64, 0, st>>>(A);
+    pair_counts_2d_walk_kernel<kPeriodic, false, Policy, kObserver><<<blocks, kWaves * 64, 0, st>>>(A);
 }
 
-// What the two entry points share: the argument checks, the zeroed result, one walk per slice of
-// rows and the cumulate. A: the policy's arguments, its own fields set by the caller.
-template <class Policy>
-int run_pairs_2d(const char *what, typename Policy::args &A, const lsk_tree_view *tree, const float *qpts,
-                 int64_t nq, const float *a2, int32_t na, const float *b2, int32_t nb, int32_t mode, int32_t los,
-                 const float *period, const uint32_t *out_perm, int64_t *out, unsigned long long *stats,
-                 void *stream) {
+// What the entry points share: the argument checks, the zeroed result, one walk per slice of
+// rows and the cumulate. A: the policy's arguments, its own fields set by the caller. kObserver:
+// observer = three finite host floats, a2_host / b2_host = host copies of a2 / b2 (for the slices'
+// cull2), los = 0 and period = null.
+template <class Policy, bool kObserver = false>
+int run_pairs_2d(const char *what, typename WalkArgs<Policy, kObserver>::type &A, const lsk_tree_view *tree,
+                 const float *qpts, int64_t nq, const float *a2, int32_t na, const float *b2, int32_t nb,
+                 int32_t mode, int32_t los, const float *period, const uint32_t *out_perm, int64_t *out,
+                 unsigned long long *stats, void *stream, const float *observer = nullptr,
+                 const float *a2_host = nullptr, const float *b2_host = nullptr) {
   if (!lsk_tree_ok(tree) || nq < 0 || nq >= ((int64_t)1 << 32) || na < 1 || na > kMaxEdges || nb < 1 ||
       nb > kMaxEdges || (int64_t)na * nb > kMaxGrid || mode < 0 || mode > 1 || los < 0 || los > 2) {
     lsk::set_last_error(std::string(what) + ": tree view incomplete (1 <= n < 2^31, depth = tree_depth(n)), "
@@ -449,9 +535,18 @@ int run_pairs_2d(const char *what, typename Policy::args &A, const lsk_tree_view
       return 1;
     }
   }
-  if (!out || !a2 || !b2 || (nq > 0 && (!qpts || !out_perm))) {
+  if (!out || !a2 || !b2 || (nq > 0 && (!qpts || !out_perm)) || (kObserver && (!observer || !a2_host || !b2_host))) {
     lsk::set_last_error(std::string(what) + ": null argument");
     return 1;
+  }
+  if constexpr (kObserver) {
+    for (int a = 0; a < 3; a++) {
+      A.o[a] = observer[a];
+      if (!std::isfinite(A.o[a])) {
+        lsk::set_last_error(std::string(what) + ": observer must be three finite values");
+        return 1;
+      }
+    }
   }
   hipStream_t st = (hipStream_t)stream;
   LSK_HIP(lsk_fill32(out, 0u, (int64_t)na * nb * 2, st));
@@ -472,7 +567,12 @@ int run_pairs_2d(const char *what, typename Policy::args &A, const lsk_tree_view
   for (int32_t r0 = 0; r0 < na; r0 += rows) {
     A.r0 = r0;
     A.r1 = std::min(na, r0 + rows);
-    if (period)
+    if constexpr (kObserver) {
+      // (rp, pi): the float after A + B (the header's proof); (s, mu): the slice's largest cs2
+      const float top = a2_host[A.r1 - 1];
+      A.cull2 = mode == 1 ? top : nextafterf((float)((double)top + (double)b2_host[nb - 1]), __builtin_inff());
+      launch_walk<false, Policy, true>(A, mode == 1, blocks, st);
+    } else if (period)
       launch_walk<true, Policy>(A, mode == 1, blocks, st);
     else
       launch_walk<false, Policy>(A, mode == 1, blocks, st);
@@ -512,4 +612,33 @@ extern "C" int lsk_hip_weighted_pair_sums_2d(const lsk_tree_view *tree, const fl
   A.wq = wq;
   return run_pairs_2d<WeightPolicy>("weighted_pair_sums_2d", A, tree, qpts, nq, a2, na, b2, nb, mode, los, period,
                                     out_perm, out, stats, stream);
+}
+
+extern "C" int lsk_hip_pair_counts_2d_observer(const lsk_tree_view *tree, const float *qpts, int64_t nq,
+                                               const float *a2, const float *a2_host, int32_t na, const float *b2,
+                                               const float *b2_host, int32_t nb, int32_t mode,
+                                               const float *observer, const uint32_t *out_perm, int64_t *out,
+                                               unsigned long long *stats, void *stream) {
+  ObserverArgs<Pair2dArgs> A{};
+  return run_pairs_2d<CountPolicy, true>("pair_counts_2d_observer", A, tree, qpts, nq, a2, na, b2, nb, mode, 0,
+                                         nullptr, out_perm, out, stats, stream, observer, a2_host, b2_host);
+}
+
+extern "C" int lsk_hip_weighted_pair_sums_2d_observer(const lsk_tree_view *tree, const float *qpts, int64_t nq,
+                                                      const float *a2, const float *a2_host, int32_t na,
+                                                      const float *b2, const float *b2_host, int32_t nb,
+                                                      int32_t mode, const float *observer,
+                                                      const uint32_t *out_perm, const int64_t *wsorted,
+                                                      const int64_t *wpre, const int64_t *wq, int64_t *out,
+                                                      unsigned long long *stats, void *stream) {
+  if (nq > 0 && (!wsorted || !wpre)) {
+    lsk::set_last_error("weighted_pair_sums_2d_observer: null argument");
+    return 1;
+  }
+  ObserverArgs<WeightedPair2dArgs> A{};
+  A.wsorted = wsorted;
+  A.wpre = wpre;
+  A.wq = wq;
+  return run_pairs_2d<WeightPolicy, true>("weighted_pair_sums_2d_observer", A, tree, qpts, nq, a2, na, b2, nb, mode,
+                                          0, nullptr, out_perm, out, stats, stream, observer, a2_host, b2_host);
 }

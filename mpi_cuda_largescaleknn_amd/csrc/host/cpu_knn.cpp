@@ -538,9 +538,13 @@ extern "C" void lsk_cpu_weighted_profile(const float *pts, int64_t n, const floa
 // b2[j] * d2)} (one float32 product). A pair with i0 == na or j0 == nb is dropped. Every thread
 // counts differential cells of its own; out [na, nb] is the 2-D prefix sum of their total.
 // w (with wq: optional) null: every pair adds 1; else wq[q] * w[i] (wq null: w[i]), wrapping.
+// obs (open box; los and period unused): the line of sight of each pair is the direction from the
+// observer obs[0 .. 3) to its midpoint. With l = (q - o) + (p - o) per axis, sl = fmaf(dz, lz,
+// fmaf(dy, ly, dx * lx)) and ll = dist2(l): par2 = (sl / ll) * sl, perp2 = d2 - par2 clamped at 0
+// from below (a NaN stays a NaN), d2 as before; the cells are the same.
 static void pair_sums_2d(const float *pts, int64_t n, const float *qry, int64_t nq, const float *a2, int32_t na,
                          const float *b2, int32_t nb, int mode, int los, const float *period, const int64_t *w,
-                         const int64_t *wq, int64_t *out, int nthreads) {
+                         const int64_t *wq, int64_t *out, int nthreads, const float *obs = nullptr) {
   const vec3f *P = (const vec3f *)pts;
   const vec3f *Q = (const vec3f *)qry;
   if (na <= 0 || nb <= 0) return;
@@ -555,9 +559,22 @@ static void pair_sums_2d(const float *pts, int64_t n, const float *qry, int64_t 
         float d[3] = {Q[qi].x - P[i].x, Q[qi].y - P[i].y, Q[qi].z - P[i].z};
         if (period)
           for (int a = 0; a < 3; a++) d[a] = wrap_diff(d[a], period[a]);
-        const float dl = d[los], da = d[los == 0 ? 1 : 0], db = d[los == 2 ? 1 : 2];
-        const float par2 = dl * dl;
-        const float va = mode == 0 ? fmaf(db, db, da * da) : lsk::dist2(d[0], d[1], d[2]);
+        float par2, va;
+        if (obs) {
+          const float lx = (Q[qi].x - obs[0]) + (P[i].x - obs[0]), ly = (Q[qi].y - obs[1]) + (P[i].y - obs[1]),
+                      lz = (Q[qi].z - obs[2]) + (P[i].z - obs[2]);
+          const float sl = fmaf(d[2], lz, fmaf(d[1], ly, d[0] * lx));
+          const float ll = lsk::dist2(lx, ly, lz);
+          const float d2 = lsk::dist2(d[0], d[1], d[2]);
+          par2 = (sl / ll) * sl;
+          float perp2 = d2 - par2;
+          if (perp2 < 0.f) perp2 = 0.f;
+          va = mode == 0 ? perp2 : d2;
+        } else {
+          const float dl = d[los], da = d[los == 0 ? 1 : 0], db = d[los == 2 ? 1 : 2];
+          par2 = dl * dl;
+          va = mode == 0 ? fmaf(db, db, da * da) : lsk::dist2(d[0], d[1], d[2]);
+        }
         const float *ia = std::partition_point(a2, a2 + na, [va](float c) { return !(va < c); });
         if (ia == a2 + na) continue;
         const float *jb = mode == 0
@@ -593,6 +610,21 @@ extern "C" void lsk_cpu_weighted_pair_sums_2d(const float *pts, int64_t n, const
                                               int los, const float *period, const int64_t *w, const int64_t *wq,
                                               int64_t *out, int nthreads) {
   pair_sums_2d(pts, n, qry, nq, a2, na, b2, nb, mode, los, period, w, wq, out, nthreads);
+}
+
+// The two above with the line of sight of an observer (three finite floats) in the place of an
+// axis: open box, pair_sums_2d with obs.
+extern "C" void lsk_cpu_pair_counts_2d_observer(const float *pts, int64_t n, const float *qry, int64_t nq,
+                                                const float *a2, int32_t na, const float *b2, int32_t nb, int mode,
+                                                const float *observer, int64_t *out, int nthreads) {
+  pair_sums_2d(pts, n, qry, nq, a2, na, b2, nb, mode, 0, nullptr, nullptr, nullptr, out, nthreads, observer);
+}
+
+extern "C" void lsk_cpu_weighted_pair_sums_2d_observer(const float *pts, int64_t n, const float *qry, int64_t nq,
+                                                       const float *a2, int32_t na, const float *b2, int32_t nb,
+                                                       int mode, const float *observer, const int64_t *w,
+                                                       const int64_t *wq, int64_t *out, int nthreads) {
+  pair_sums_2d(pts, n, qry, nq, a2, na, b2, nb, mode, 0, nullptr, w, wq, out, nthreads, observer);
 }
 
 // lsk_cpu_kth_brute under a period: the k-th smallest pdist2 among those < cut2, else cut2.

@@ -155,6 +155,18 @@ void lsk_cpu_pair_counts_2d(const float *pts, int64_t n, const float *qry, int64
 void lsk_cpu_weighted_pair_sums_2d(const float *pts, int64_t n, const float *qry, int64_t nq, const float *a2,
                                    int32_t na, const float *b2, int32_t nb, int mode, int los, const float *period,
                                    const int64_t *w, const int64_t *wq, int64_t *out, int nthreads);
+// The two above in the open box with the line of sight of an observer (three finite floats) in the
+// place of an axis: per pair l = (q - o) + (p - o) per axis (twice observer -> midpoint), sl =
+// fmaf(dz, lz, fmaf(dy, ly, dx * lx)), ll = dist2(l), par2 = (sl / ll) * sl, perp2 = d2 - par2, a
+// negative perp2 becoming 0 and a NaN staying one; the same cells. A pair whose midpoint is the
+// observer (ll == 0) counts nowhere.
+void lsk_cpu_pair_counts_2d_observer(const float *pts, int64_t n, const float *qry, int64_t nq, const float *a2,
+                                     int32_t na, const float *b2, int32_t nb, int mode, const float *observer,
+                                     int64_t *out, int nthreads);
+void lsk_cpu_weighted_pair_sums_2d_observer(const float *pts, int64_t n, const float *qry, int64_t nq,
+                                            const float *a2, int32_t na, const float *b2, int32_t nb, int mode,
+                                            const float *observer, const int64_t *w, const int64_t *wq,
+                                            int64_t *out, int nthreads);
 // lsk_cpu_kth_brute / lsk_cpu_knn_brute under a period: brute force over all points with the
 // periodic squared distance above, the same selection (k-th smallest by bits among those <
 // cut2, else cut2) and the same tie rule (ascending (d² bits, row); unfilled: -1 / cut2).

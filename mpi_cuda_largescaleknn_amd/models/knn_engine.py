@@ -1711,7 +1711,8 @@ def pair_self_counts(points: torch.Tensor, radii, squared: bool = False, period=
     return pair_query_counts(points, points, radii, squared=squared, period=period, stats=stats)
 
 
-# ---- anisotropic pair counts: DD(rp, pi) and DD(s, mu) along a box axis (pair_counts_2d.hip)
+# ---- anisotropic pair counts: DD(rp, pi) and DD(s, mu) along a box axis or an observer's line
+# of sight (pair_counts_2d.hip)
 _LOS = {"x": 0, "y": 1, "z": 2}
 
 
@@ -1737,23 +1738,32 @@ def _edge_values(what: str, name: str, edges) -> list:
     return vals
 
 
-def _pairs2d_cutoffs(what: str, mode: str, first, second, los, squared: bool, period) -> tuple:
+def _pairs2d_cutoffs(what: str, mode: str, first, second, los, squared: bool, period, observer=None) -> tuple:
     """The checked arguments of an anisotropic pair count: (a2, b2 float32 CPU tensors, los in {0,
     1, 2}, period values or None). mode 'rppi': first = rp, second = pi; 'smu': first = s, second
     = mu (always plain mu, squared by cut2_of). Under a period a line-of-sight radius (pi, s) may
     not exceed period_radius_bound of the line-of-sight axis and a perpendicular radius (rp, s)
-    not that of the two other axes. ValueError otherwise; nothing on a device is read."""
-    if isinstance(los, str):
-        los = _LOS.get(los.lower(), -1)
-    if isinstance(los, bool) or not isinstance(los, int) or los not in (0, 1, 2):
-        raise ValueError(f"{what}: los must be 0, 1, 2 or 'x', 'y', 'z'")
+    not that of the two other axes. los='midpoint': the third entry is the observer, a tuple of
+    three finite float32 values (`observer`, None: the origin), and there is no period; an observer
+    goes with no other los. ValueError otherwise; nothing on a device is read."""
+    if isinstance(los, str) and los.lower() == "midpoint":
+        if period is not None:
+            raise ValueError(f"{what}: los='midpoint' has no period (a periodic box has no observer)")
+        los = K.check_observer(what, (0.0, 0.0, 0.0) if observer is None else observer)
+    else:
+        if isinstance(los, str):
+            los = _LOS.get(los.lower(), -1)
+        if isinstance(los, bool) or not isinstance(los, int) or los not in (0, 1, 2):
+            raise ValueError(f"{what}: los must be 0, 1, 2, 'x', 'y', 'z' or 'midpoint'")
+        if observer is not None:
+            raise ValueError(f"{what}: an observer goes with los='midpoint' only (got los={los})")
     n1, n2 = ("rp", "pi") if mode == "rppi" else ("s", "mu")
     v1, v2 = _edge_values(what, n1, first), _edge_values(what, n2, second)
     if len(v1) * len(v2) > K.PAIRS2D_MAX_CELLS:
         raise ValueError(f"{what}: {len(v1)} x {len(v2)} cells exceed {K.PAIRS2D_MAX_CELLS}")
     per = None if period is None else K.check_period(what, period)
     if per is not None:
-        along = period_radius_bound((per[los],), squared)
+        along = period_radius_bound((per[los],), squared)  # (an observer has no period: los is an axis)
         across = period_radius_bound(tuple(per[a] for a in range(3) if a != los), squared)
         for nm, vals, upper, axis in ((n1, v1, across, "a perpendicular axis"),
                                       (n1, v1 if mode == "smu" else (), along, "the line-of-sight axis"),
@@ -1768,8 +1778,9 @@ def _pairs2d_cutoffs(what: str, mode: str, first, second, los, squared: bool, pe
 
 
 def _pairs2d(what: str, mode: str, index: LocalIndex, queries: torch.Tensor, first, second, los, squared: bool,
-             period, stats: KnnStats | None) -> torch.Tensor:
-    a2, b2, los, per = _pairs2d_cutoffs(what, mode, first, second, los, squared, period)
+             period, stats: KnnStats | None, observer=None) -> torch.Tensor:
+    a2, b2, los, per = _pairs2d_cutoffs(what, mode, first, second, los, squared, period, observer)
+    midpoint = isinstance(los, tuple)  # the observer itself
     if index.qrot is not None or index.line:
         raise ValueError(f"{what}: an index built in a rotated frame or sorted by line keys is not supported")
     queries = _check_foreign(what, index, queries)
@@ -1778,12 +1789,18 @@ def _pairs2d(what: str, mode: str, index: LocalIndex, queries: torch.Tensor, fir
         return torch.zeros((a2.shape[0], b2.shape[0]), dtype=torch.int64, device=index.device)
     if not K.is_gpu(index.pts):
         KERNELS_USED.add("cpu")
+        if midpoint:
+            return K.pair_counts_2d_observer_cpu(index.pts[:n], queries, a2, b2, mode, los)
         return K.pair_counts_2d_cpu(index.pts[:n], queries, a2, b2, mode, los, per)
     qsorted, qperm = prepare_queries(index, queries, locate=False)[:2]
     names = _RADIUS_STATS if per is None else _RADIUS_PERIODIC_STATS
     raw = torch.zeros(len(names), dtype=torch.int64, device=index.device) if stats is not None else None
-    out = K.pair_counts_2d_gpu(index.tree(), qsorted, nq, a2, b2, mode, los, qperm, per, stats=raw)
-    KERNELS_USED.add("pair_counts_2d")
+    if midpoint:
+        out = K.pair_counts_2d_observer_gpu(index.tree(), qsorted, nq, a2, b2, mode, los, qperm, stats=raw)
+        KERNELS_USED.add("pair_counts_2d_observer")
+    else:
+        out = K.pair_counts_2d_gpu(index.tree(), qsorted, nq, a2, b2, mode, los, qperm, per, stats=raw)
+        KERNELS_USED.add("pair_counts_2d")
     if stats is not None:
         for nm, v in zip(names, raw.cpu().tolist()):
             stats.counters[nm] = stats.counters.get(nm, 0) + int(v)
@@ -1791,19 +1808,19 @@ def _pairs2d(what: str, mode: str, index: LocalIndex, queries: torch.Tensor, fir
 
 
 def _pairs2d_index(what: str, mode: str, points: torch.Tensor, queries: torch.Tensor, first, second, los,
-                   squared: bool, period) -> tuple:
+                   squared: bool, period, observer=None) -> tuple:
     """(index or None, the empty result) of the *_query_* / *_self_* forms (the arguments are
     checked all the same when there is nothing to index)."""
     if points.device != queries.device:
         raise ValueError(f"{what}: points on {points.device}, queries on {queries.device}")
+    a2, b2 = _pairs2d_cutoffs(what, mode, first, second, los, squared, period, observer)[:2]  # (before the index)
     if points.shape[0] == 0:
-        a2, b2 = _pairs2d_cutoffs(what, mode, first, second, los, squared, period)[:2]
         return None, torch.zeros((a2.shape[0], b2.shape[0]), dtype=torch.int64, device=queries.device)
     return build_index(points), None
 
 
 def pair_counts_rppi(index: LocalIndex, queries: torch.Tensor, rp, pi, los=2, squared: bool = False, period=None,
-                     stats: KnnStats | None = None) -> torch.Tensor:
+                     stats: KnnStats | None = None, observer=None) -> torch.Tensor:
     """int64 [Bp, Bl] on the index's device: S[i, j] = the number of pairs (query q, indexed point
     p) with perp2 < cut2_of(rp[i]) and par2 < cut2_of(pi[j]), strict and cumulative on both axes:
     the DD / DR counts of the projected two-point function along a box axis, from one walk of the
@@ -1822,29 +1839,48 @@ def pair_counts_rppi(index: LocalIndex, queries: torch.Tensor, rp, pi, los=2, sq
     supported. `stats` receives the radius_* counters of radius_profile. Grids of more than 2048
     cells are served in slices of whole rp rows, one walk each. Integer sums: two runs give the
     same bits. Limit as for radius_profile: whole boxes are counted without visiting their
-    points, which is exact for finite indexed points."""
-    return _pairs2d("pair_counts_rppi", "rppi", index, queries, rp, pi, los, squared, period, stats)
+    points, which is exact for finite indexed points.
+
+    los='midpoint' (any case) with observer=(ox, oy, oz), three finite numbers taken as float32
+    (default the origin): every pair has its own line of sight, the direction from the observer o
+    to the pair's midpoint, as in survey catalogues, light cones and mocks with randoms. Open box
+    only. Per pair, in float32 without contraction: l = (q - o) + (p - o) per axis (twice the
+    vector observer -> midpoint), sl = fmaf(dz, lz, fmaf(dy, ly, dx * lx)), ll = dist2(lx, ly,
+    lz), d2 = dist2(dx, dy, dz), par2 = (sl / ll) * sl (one correctly rounded division, one
+    product), perp2 = d2 - par2, a negative perp2 becoming 0 and a NaN staying one; the cells are
+    the same. Swapping q and p changes no bit, so the self forms count ordered pairs. A pair whose
+    midpoint is the observer (ll == 0) counts nowhere; a point with itself has par2 = perp2 = 0;
+    a NaN or infinite component or intermediate passes no test; par2 may exceed d2 by rounding
+    (perp2 is then 0). The walk culls by one ball of radius² just above cut2_of(rp) + cut2_of(pi)
+    of the slice and accepts no whole box (radius_box_accepts stays 0), so it evaluates more pairs
+    than an axis walk. A `period`, an observer without los='midpoint' and an observer that is not
+    three finite numbers raise ValueError. Not built: a periodic observer mode, sky coordinates
+    (RA, Dec, z), angular w(theta), a bisector other than the midpoint."""
+    return _pairs2d("pair_counts_rppi", "rppi", index, queries, rp, pi, los, squared, period, stats, observer)
 
 
 def pair_query_counts_rppi(points: torch.Tensor, queries: torch.Tensor, rp, pi, los=2, squared: bool = False,
-                           period=None, stats: KnnStats | None = None) -> torch.Tensor:
+                           period=None, stats: KnnStats | None = None, observer=None) -> torch.Tensor:
     """pair_counts_rppi over an index built once from `points`, in the points' own frame."""
-    index, empty = _pairs2d_index("pair_query_counts_rppi", "rppi", points, queries, rp, pi, los, squared, period)
+    index, empty = _pairs2d_index("pair_query_counts_rppi", "rppi", points, queries, rp, pi, los, squared, period,
+                                  observer)
     if index is None:
         return empty
-    return pair_counts_rppi(index, queries, rp, pi, los=los, squared=squared, period=period, stats=stats)
+    return pair_counts_rppi(index, queries, rp, pi, los=los, squared=squared, period=period, stats=stats,
+                            observer=observer)
 
 
 def pair_self_counts_rppi(points: torch.Tensor, rp, pi, los=2, squared: bool = False, period=None,
-                          stats: KnnStats | None = None) -> torch.Tensor:
+                          stats: KnnStats | None = None, observer=None) -> torch.Tensor:
     """pair_query_counts_rppi with the points as their own queries: ordered pairs, (p, q) and (q,
     p) both, and every finite point with itself (perp2 = par2 = 0: in every cell with cutoffs >
     0), like pair_self_counts."""
-    return pair_query_counts_rppi(points, points, rp, pi, los=los, squared=squared, period=period, stats=stats)
+    return pair_query_counts_rppi(points, points, rp, pi, los=los, squared=squared, period=period, stats=stats,
+                                  observer=observer)
 
 
 def pair_counts_smu(index: LocalIndex, queries: torch.Tensor, s, mu, los=2, squared: bool = False, period=None,
-                    stats: KnnStats | None = None) -> torch.Tensor:
+                    stats: KnnStats | None = None, observer=None) -> torch.Tensor:
     """int64 [Bs, Bm] on the index's device: S[i, j] = the number of pairs with d2 < cut2_of(s[i])
     and par2 < mu2[j] * d2 (one float32 product), mu2[j] = cut2_of(mu[j]): the cumulative counts of
     DD(s, mu) for the multipoles, mu = |dl| / s being the cosine to the line of sight. d2 is the
@@ -1854,24 +1890,29 @@ def pair_counts_smu(index: LocalIndex, queries: torch.Tensor, s, mu, los=2, squa
     copies) counts in no column, and an edge mu = 1 excludes the pairs that lie exactly along the
     line of sight, which an edge of inf takes in. Under a period every s may exceed neither the
     bound of the line-of-sight axis nor that of a perpendicular axis. Everything else as for
-    pair_counts_rppi; there is no whole-box acceptance in this mode."""
-    return _pairs2d("pair_counts_smu", "smu", index, queries, s, mu, los, squared, period, stats)
+    pair_counts_rppi; there is no whole-box acceptance in this mode. los='midpoint' and observer as
+    for pair_counts_rppi, with its d2 and par2: since par2 may exceed d2 by rounding, an edge mu =
+    1 excludes such a pair as well and an edge of inf takes it in; the cull is the ball of s."""
+    return _pairs2d("pair_counts_smu", "smu", index, queries, s, mu, los, squared, period, stats, observer)
 
 
 def pair_query_counts_smu(points: torch.Tensor, queries: torch.Tensor, s, mu, los=2, squared: bool = False,
-                          period=None, stats: KnnStats | None = None) -> torch.Tensor:
+                          period=None, stats: KnnStats | None = None, observer=None) -> torch.Tensor:
     """pair_counts_smu over an index built once from `points`, in the points' own frame."""
-    index, empty = _pairs2d_index("pair_query_counts_smu", "smu", points, queries, s, mu, los, squared, period)
+    index, empty = _pairs2d_index("pair_query_counts_smu", "smu", points, queries, s, mu, los, squared, period,
+                                  observer)
     if index is None:
         return empty
-    return pair_counts_smu(index, queries, s, mu, los=los, squared=squared, period=period, stats=stats)
+    return pair_counts_smu(index, queries, s, mu, los=los, squared=squared, period=period, stats=stats,
+                           observer=observer)
 
 
 def pair_self_counts_smu(points: torch.Tensor, s, mu, los=2, squared: bool = False, period=None,
-                         stats: KnnStats | None = None) -> torch.Tensor:
+                         stats: KnnStats | None = None, observer=None) -> torch.Tensor:
     """pair_query_counts_smu with the points as their own queries: ordered pairs; a point with
     itself (d2 == 0) counts nowhere."""
-    return pair_query_counts_smu(points, points, s, mu, los=los, squared=squared, period=period, stats=stats)
+    return pair_query_counts_smu(points, points, s, mu, los=los, squared=squared, period=period, stats=stats,
+                                 observer=observer)
 
 
 def shell_counts_2d(S: torch.Tensor) -> torch.Tensor:
@@ -2095,8 +2136,10 @@ def weighted_pair_self_sums(points: torch.Tensor, radii, weights: torch.Tensor,
 
 # ---- weighted anisotropic pair sums: weights on DD(rp, pi) and DD(s, mu) (pair_counts_2d.hip)
 def _weighted_pairs2d(what: str, mode: str, index: LocalIndex, queries: torch.Tensor, first, second, weights,
-                      query_weights, los, squared: bool, period, stats: KnnStats | None) -> torch.Tensor:
-    a2, b2, los, per = _pairs2d_cutoffs(what, mode, first, second, los, squared, period)
+                      query_weights, los, squared: bool, period, stats: KnnStats | None,
+                      observer=None) -> torch.Tensor:
+    a2, b2, los, per = _pairs2d_cutoffs(what, mode, first, second, los, squared, period, observer)
+    midpoint = isinstance(los, tuple)  # the observer itself
     if index.qrot is not None or index.line:
         raise ValueError(f"{what}: an index built in a rotated frame or sorted by line keys is not supported")
     queries = _check_foreign(what, index, queries)
@@ -2110,14 +2153,22 @@ def _weighted_pairs2d(what: str, mode: str, index: LocalIndex, queries: torch.Te
         return torch.zeros((a2.shape[0], b2.shape[0]), dtype=torch.int64, device=index.device)
     if not K.is_gpu(index.pts):
         KERNELS_USED.add("cpu")
+        if midpoint:
+            return K.weighted_pair_sums_2d_observer_cpu(index.pts[:n], queries, a2, b2, pw.sorted, mode, los,
+                                                        query_weights=wq)
         return K.weighted_pair_sums_2d_cpu(index.pts[:n], queries, a2, b2, pw.sorted, mode, los, per,
                                            query_weights=wq)
     qsorted, qperm = prepare_queries(index, queries, locate=False)[:2]
     names = _RADIUS_STATS if per is None else _RADIUS_PERIODIC_STATS
     raw = torch.zeros(len(names), dtype=torch.int64, device=index.device) if stats is not None else None
-    out = K.weighted_pair_sums_2d_gpu(index.tree(), qsorted, nq, a2, b2, mode, los, qperm, pw.sorted, pw.prefix,
-                                      period=per, query_weights=wq, stats=raw)
-    KERNELS_USED.add("weighted_pair_sums_2d")
+    if midpoint:
+        out = K.weighted_pair_sums_2d_observer_gpu(index.tree(), qsorted, nq, a2, b2, mode, los, qperm, pw.sorted,
+                                                   pw.prefix, query_weights=wq, stats=raw)
+        KERNELS_USED.add("weighted_pair_sums_2d_observer")
+    else:
+        out = K.weighted_pair_sums_2d_gpu(index.tree(), qsorted, nq, a2, b2, mode, los, qperm, pw.sorted, pw.prefix,
+                                          period=per, query_weights=wq, stats=raw)
+        KERNELS_USED.add("weighted_pair_sums_2d")
     if stats is not None:
         for nm, v in zip(names, raw.cpu().tolist()):
             stats.counters[nm] = stats.counters.get(nm, 0) + int(v)
@@ -2126,21 +2177,22 @@ def _weighted_pairs2d(what: str, mode: str, index: LocalIndex, queries: torch.Te
 
 def _weighted_pairs2d_points(what: str, mode: str, points: torch.Tensor, queries: torch.Tensor, first, second,
                              weights, query_weights, los, squared: bool, period,
-                             stats: KnnStats | None) -> torch.Tensor:
+                             stats: KnnStats | None, observer=None) -> torch.Tensor:
     """The *_query_* / *_self_* forms: an index built once from `points` (the arguments are checked
     all the same when there is nothing to index)."""
-    index, empty = _pairs2d_index(what, mode, points, queries, first, second, los, squared, period)
+    index, empty = _pairs2d_index(what, mode, points, queries, first, second, los, squared, period, observer)
     if index is None:
         K.int64_weights(what, "weights", weights, 0, points.device)
         if query_weights is not None:
             K.int64_weights(what, "query_weights", query_weights, queries.shape[0], queries.device)
         return empty
     return _weighted_pairs2d(what, mode, index, queries, first, second, weights, query_weights, los, squared,
-                             period, stats)
+                             period, stats, observer)
 
 
 def weighted_pair_sums_rppi(index: LocalIndex, queries: torch.Tensor, rp, pi, weights, query_weights=None, los=2,
-                            squared: bool = False, period=None, stats: KnnStats | None = None) -> torch.Tensor:
+                            squared: bool = False, period=None, stats: KnnStats | None = None,
+                            observer=None) -> torch.Tensor:
     """int64 [Bp, Bl] on the index's device: WS[i, j] = the sum of query_weights[q] * weights[p]
     over the pairs (query q, indexed point p) with perp2 < cut2_of(rp[i]) and par2 < cut2_of(pi[j]),
     strict and cumulative on both axes: pair_counts_rppi with a weight per point and per query in
@@ -2159,58 +2211,59 @@ def weighted_pair_sums_rppi(index: LocalIndex, queries: torch.Tensor, rp, pi, we
     coordinate adds nothing. Weights of another dtype, shape or device, weights prepared for
     another index, either bound exceeded and every argument error of pair_counts_rppi raise
     ValueError; an index built in a rotated frame or sorted by line keys is not supported. `stats`
-    receives the radius_* counters."""
+    receives the radius_* counters. los='midpoint' and observer as for pair_counts_rppi."""
     return _weighted_pairs2d("weighted_pair_sums_rppi", "rppi", index, queries, rp, pi, weights, query_weights, los,
-                             squared, period, stats)
+                             squared, period, stats, observer)
 
 
 def weighted_pair_query_sums_rppi(points: torch.Tensor, queries: torch.Tensor, rp, pi, weights: torch.Tensor,
                                   query_weights: torch.Tensor | None = None, los=2, squared: bool = False,
-                                  period=None, stats: KnnStats | None = None) -> torch.Tensor:
+                                  period=None, stats: KnnStats | None = None, observer=None) -> torch.Tensor:
     """weighted_pair_sums_rppi over an index built once from `points`, in the points' own frame."""
     return _weighted_pairs2d_points("weighted_pair_query_sums_rppi", "rppi", points, queries, rp, pi, weights,
-                                    query_weights, los, squared, period, stats)
+                                    query_weights, los, squared, period, stats, observer)
 
 
 def weighted_pair_self_sums_rppi(points: torch.Tensor, rp, pi, weights: torch.Tensor,
                                  query_weights: torch.Tensor | None = None, los=2, squared: bool = False,
-                                 period=None, stats: KnnStats | None = None) -> torch.Tensor:
+                                 period=None, stats: KnnStats | None = None, observer=None) -> torch.Tensor:
     """weighted_pair_query_sums_rppi with the points as their own queries and, unless query_weights
     is given, `weights` on both sides: ordered pairs, (p, q) and (q, p) both, and every finite point
     with itself (perp2 = par2 = 0: w[p]^2 in every cell with cutoffs > 0), like
     weighted_pair_self_sums."""
     return _weighted_pairs2d_points("weighted_pair_self_sums_rppi", "rppi", points, points, rp, pi, weights,
                                     weights if query_weights is None else query_weights, los, squared, period,
-                                    stats)
+                                    stats, observer)
 
 
 def weighted_pair_sums_smu(index: LocalIndex, queries: torch.Tensor, s, mu, weights, query_weights=None, los=2,
-                           squared: bool = False, period=None, stats: KnnStats | None = None) -> torch.Tensor:
+                           squared: bool = False, period=None, stats: KnnStats | None = None,
+                           observer=None) -> torch.Tensor:
     """int64 [Bs, Bm] on the index's device: WS[i, j] = the sum of query_weights[q] * weights[p]
     over the pairs with d2 < cut2_of(s[i]) and par2 < mu2[j] * d2: pair_counts_smu with weights, as
     weighted_pair_sums_rppi is pair_counts_rppi with weights. A pair with d2 == 0 adds to no cell;
     there is no whole-box acceptance in this mode. s, mu and everything else as for
     pair_counts_smu, weights and errors as for weighted_pair_sums_rppi."""
     return _weighted_pairs2d("weighted_pair_sums_smu", "smu", index, queries, s, mu, weights, query_weights, los,
-                             squared, period, stats)
+                             squared, period, stats, observer)
 
 
 def weighted_pair_query_sums_smu(points: torch.Tensor, queries: torch.Tensor, s, mu, weights: torch.Tensor,
                                  query_weights: torch.Tensor | None = None, los=2, squared: bool = False,
-                                 period=None, stats: KnnStats | None = None) -> torch.Tensor:
+                                 period=None, stats: KnnStats | None = None, observer=None) -> torch.Tensor:
     """weighted_pair_sums_smu over an index built once from `points`, in the points' own frame."""
     return _weighted_pairs2d_points("weighted_pair_query_sums_smu", "smu", points, queries, s, mu, weights,
-                                    query_weights, los, squared, period, stats)
+                                    query_weights, los, squared, period, stats, observer)
 
 
 def weighted_pair_self_sums_smu(points: torch.Tensor, s, mu, weights: torch.Tensor,
                                 query_weights: torch.Tensor | None = None, los=2, squared: bool = False,
-                                period=None, stats: KnnStats | None = None) -> torch.Tensor:
+                                period=None, stats: KnnStats | None = None, observer=None) -> torch.Tensor:
     """weighted_pair_query_sums_smu with the points as their own queries and, unless query_weights is
     given, `weights` on both sides: ordered pairs; a point with itself (d2 == 0) adds nowhere."""
     return _weighted_pairs2d_points("weighted_pair_self_sums_smu", "smu", points, points, s, mu, weights,
                                     weights if query_weights is None else query_weights, los, squared, period,
-                                    stats)
+                                    stats, observer)
 
 
 def fixed_point_weights(weights: torch.Tensor, n_terms: int | None = None, bits: int = 62) -> tuple:

@@ -1326,6 +1326,59 @@ def pair_counts_2d_gpu(tree: tuple, qsorted: torch.Tensor, nq: int, a2, b2, mode
     return res
 
 
+def check_observer(what: str, observer) -> tuple[float, float, float]:
+    """(ox, oy, oz) as float32 values, each finite. Anything else raises ValueError."""
+    if isinstance(observer, torch.Tensor):
+        observer = observer.detach().cpu().tolist()
+    try:
+        vals = tuple(float(torch.tensor(float(v), dtype=torch.float32)) for v in observer)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"{what}: observer must be three finite numbers (got {observer!r})") from None
+    if len(vals) != 3 or not all(math.isfinite(v) for v in vals):
+        raise ValueError(f"{what}: observer must be three finite numbers (got {observer!r})")
+    return vals
+
+
+def pair_counts_2d_observer_cpu(points: torch.Tensor, queries: torch.Tensor, a2, b2, mode: str,
+                                observer=(0.0, 0.0, 0.0)) -> torch.Tensor:
+    """CPU oracle (brute force over all pairs) of the anisotropic pair counts with the line of sight
+    of an observer: pair_counts_2d_cpu in the open box with, per pair, l = (q - o) + (p - o) per
+    axis (twice the vector observer -> midpoint), sl = fmaf(dz, lz, fmaf(dy, ly, dx * lx)), ll =
+    dist2(l), par2 = (sl / ll) * sl and perp2 = d2 - par2 (a negative one becomes 0, a NaN stays),
+    all float32. A pair whose midpoint is the observer counts nowhere."""
+    what = "pair_counts_2d_observer_cpu"
+    a, b = _pairs2d_args(what, a2, b2, mode, 0)
+    obs = check_observer(what, observer)
+    pts = points.contiguous().float().cpu()
+    q = queries.contiguous().float().cpu()
+    out = torch.zeros((a.shape[0], b.shape[0]), dtype=torch.int64)
+    _native.host().lsk_cpu_pair_counts_2d_observer(_ptr(pts), pts.shape[0], _ptr(q), q.shape[0], _ptr(a), a.shape[0],
+                                                   _ptr(b), b.shape[0], PAIRS2D_MODES[mode], _period_c(obs),
+                                                   _ptr(out), _nthreads())
+    return out
+
+
+def pair_counts_2d_observer_gpu(tree: tuple, qsorted: torch.Tensor, nq: int, a2, b2, mode: str, observer,
+                                out_perm: torch.Tensor, stats: torch.Tensor | None = None) -> torch.Tensor:
+    """The observer walk of pair_counts_2d.hip on the current stream: int64 [Ba, Bb] on the tree's
+    device, what pair_counts_2d_observer_cpu defines. Open box; the cull is a ball per slice whose
+    radius the library takes from the host copies of the cutoffs; no whole-box acceptance (word 3
+    of stats stays 0). Everything else as for pair_counts_2d_gpu."""
+    what = "pair_counts_2d_observer_gpu"
+    a, b = _pairs2d_args(what, a2, b2, mode, 0)
+    obs = check_observer(what, observer)
+    tv = _walk_view(what, tree, qsorted, nq, out_perm)
+    dev = tree[0].device
+    _profile_stats(what, stats, None, dev)
+    res = torch.empty((a.shape[0], b.shape[0]), dtype=torch.int64, device=dev)
+    adev, bdev = a.to(dev), b.to(dev)
+    check(_native.hip().lsk_hip_pair_counts_2d_observer(
+        C.byref(tv), _ptr(qsorted), int(nq), _ptr(adev), _ptr(a), a.shape[0], _ptr(bdev), _ptr(b), b.shape[0],
+        PAIRS2D_MODES[mode], _period_c(obs), _ptr(out_perm), _ptr(res), _ptr(stats), _stream(tree[0])),
+        "pair_counts_2d_observer")
+    return res
+
+
 # --------------------------------------------------------------------------- weighted radius profiles
 def int64_weights(what: str, name: str, w, count: int, device: torch.device | None = None) -> torch.Tensor:
     """The int64 [count] weight tensor `name` of the function `what`, checked and contiguous (also
@@ -1455,6 +1508,53 @@ def weighted_pair_sums_2d_gpu(tree: tuple, qsorted: torch.Tensor, nq: int, a2, b
         C.byref(tv), _ptr(qsorted), int(nq), _ptr(adev), a.shape[0], _ptr(bdev), b.shape[0], PAIRS2D_MODES[mode],
         int(los), None if period is None else _period_c(period), _ptr(out_perm), _ptr(wsorted), _ptr(wprefix),
         _ptr(wq), _ptr(res), _ptr(stats), _stream(tree[0])), "weighted_pair_sums_2d")
+    return res
+
+
+def weighted_pair_sums_2d_observer_cpu(points: torch.Tensor, queries: torch.Tensor, a2, b2, weights: torch.Tensor,
+                                       mode: str, observer=(0.0, 0.0, 0.0),
+                                       query_weights: torch.Tensor | None = None) -> torch.Tensor:
+    """CPU oracle of the weighted anisotropic pair sums with the line of sight of an observer:
+    pair_counts_2d_observer_cpu with query_weights[q] * weights[p] added per pair in the place of 1,
+    weights and wrapping as for weighted_pair_sums_2d_cpu."""
+    what = "weighted_pair_sums_2d_observer_cpu"
+    a, b = _pairs2d_args(what, a2, b2, mode, 0)
+    obs = check_observer(what, observer)
+    pts = points.contiguous().float().cpu()
+    q = queries.contiguous().float().cpu()
+    w = int64_weights(what, "weights", weights, pts.shape[0]).cpu()
+    wq = None if query_weights is None else int64_weights(what, "query_weights", query_weights, q.shape[0]).cpu()
+    out = torch.zeros((a.shape[0], b.shape[0]), dtype=torch.int64)
+    _native.host().lsk_cpu_weighted_pair_sums_2d_observer(
+        _ptr(pts), pts.shape[0], _ptr(q), q.shape[0], _ptr(a), a.shape[0], _ptr(b), b.shape[0], PAIRS2D_MODES[mode],
+        _period_c(obs), _ptr(w), _ptr(wq), _ptr(out), _nthreads())
+    return out
+
+
+def weighted_pair_sums_2d_observer_gpu(tree: tuple, qsorted: torch.Tensor, nq: int, a2, b2, mode: str, observer,
+                                       out_perm: torch.Tensor, wsorted: torch.Tensor, wprefix: torch.Tensor,
+                                       query_weights: torch.Tensor | None = None,
+                                       stats: torch.Tensor | None = None) -> torch.Tensor:
+    """The observer walk of pair_counts_2d.hip under the weight policy: int64 [Ba, Bb] on the tree's
+    device, what weighted_pair_sums_2d_observer_cpu defines. Weights and their bounds as for
+    weighted_pair_sums_2d_gpu, everything else as for pair_counts_2d_observer_gpu."""
+    what = "weighted_pair_sums_2d_observer_gpu"
+    a, b = _pairs2d_args(what, a2, b2, mode, 0)
+    obs = check_observer(what, observer)
+    tv = _walk_view(what, tree, qsorted, nq, out_perm)
+    dev = tree[0].device
+    _profile_stats(what, stats, None, dev)
+    _weighted_args(what, tree, wsorted, wprefix)
+    wq = query_weights
+    if wq is not None and (wq.dtype != torch.int64 or wq.dim() != 1 or wq.shape[0] != nq or not wq.is_contiguous()
+                           or wq.device != dev):
+        raise ValueError(f"{what}: query_weights must be a contiguous int64 [{nq}] tensor on the tree's device")
+    res = torch.empty((a.shape[0], b.shape[0]), dtype=torch.int64, device=dev)
+    adev, bdev = a.to(dev), b.to(dev)
+    check(_native.hip().lsk_hip_weighted_pair_sums_2d_observer(
+        C.byref(tv), _ptr(qsorted), int(nq), _ptr(adev), _ptr(a), a.shape[0], _ptr(bdev), _ptr(b), b.shape[0],
+        PAIRS2D_MODES[mode], _period_c(obs), _ptr(out_perm), _ptr(wsorted), _ptr(wprefix), _ptr(wq), _ptr(res),
+        _ptr(stats), _stream(tree[0])), "weighted_pair_sums_2d_observer")
     return res
 
 

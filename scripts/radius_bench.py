@@ -8,6 +8,7 @@
                                    [--steps ..] [--warmup ..] [--period ..] [--weights]
     python scripts/radius_bench.py --pairs-2d BPxBL [--smu] [-r R] [--self-queries] [--points ..] [--queries ..]
                                    [--steps ..] [--warmup ..] [--period ..] [--skip-pair-list] [--weights]
+                                   [--los midpoint [--observer ox,oy,oz]]
 
 Uniform points in the unit cube and uniform queries from another seed; the radius is the one
 whose ball holds --mean points at the data's density (queries near the faces see fewer, so
@@ -65,6 +66,12 @@ are compared with one more, untimed pass of the pair-list route that forms perp2
 kernel does (the square exact in float64, one sum, rounded to float32: the fma but for a double
 rounding that needs a 29-bit coincidence): every cell must be equal, or the run fails. The timed
 route's own float32 cells are reported as before (the number that differ).
+
+--pairs-2d BPxBL --los midpoint [--observer ox,oy,oz] (default 0.5,0.5,-3): the observer's line of
+sight (open box). pairs2d / wpairs2d are then the observer walk; the axis walk (los z) of the same
+grid is timed beside them as pairs2d_axis / wpairs2d_axis, the pair-list route forms par2 and perp2
+of the observer contract in torch, and the JSON carries the ratios of the times and of the
+radius_evals of the two walks.
 """
 from __future__ import annotations
 
@@ -207,10 +214,13 @@ def weighted_bench(a, p: torch.Tensor, q: torch.Tensor, r: float, per: dict) -> 
 
 
 def pair_list_cells(index, p, q, R, first2, second2, smu: bool, per: dict, period, chunk: int,
-                    weights: tuple | None = None, exact: bool = False) -> torch.Tensor:
+                    weights: tuple | None = None, exact: bool = False, observer=None) -> torch.Tensor:
     """The differential [B1, B2] cells (int64) by way of the pair lists at the enclosing radius R;
     weights = (w, wq): every pair adds wq[q] * w[p] in the place of 1; exact: perp2 and d2 as the
-    float32 fma of the kernel, by way of float64."""
+    float32 fma of the kernel, by way of float64; observer: par2 and perp2 of the observer contract."""
+    def fma(a, b, c):  # exact: the product exact in float64, one sum, rounded to float32
+        return (a.double() * b.double() + c.double()).float() if exact else torch.addcmul(c, a, b)
+    obs = None if observer is None else torch.tensor(observer, dtype=torch.float32, device=q.device)
     b1, b2 = first2.shape[0], second2.shape[0]
     cells = torch.zeros(b1 * b2, dtype=torch.int64, device=q.device)
     for a in range(0, q.shape[0], chunk):
@@ -229,8 +239,17 @@ def pair_list_cells(index, p, q, R, first2, second2, smu: bool, per: dict, perio
             perp2 = (d[:, 1].double() * d[:, 1].double() + (d[:, 0] * d[:, 0]).double()).float()
         else:
             perp2 = torch.addcmul(d[:, 0] * d[:, 0], d[:, 1], d[:, 1])
+        if obs is not None:
+            l = (q[rows] - obs) + (p[idx.long()] - obs)
+            sl = fma(d[:, 2], l[:, 2], fma(d[:, 1], l[:, 1], d[:, 0] * l[:, 0]))
+            ll = fma(l[:, 2], l[:, 2], fma(l[:, 1], l[:, 1], l[:, 0] * l[:, 0]))
+            d2 = fma(d[:, 2], d[:, 2], fma(d[:, 1], d[:, 1], d[:, 0] * d[:, 0]))
+            par2 = (sl / ll) * sl
+            perp2 = d2 - par2
+            perp2 = torch.where(perp2 < 0, torch.zeros_like(perp2), perp2)
         if smu:
-            d2 = (d[:, 2].double() * d[:, 2].double() + perp2.double()).float() if exact else perp2 + par2
+            if obs is None:
+                d2 = (d[:, 2].double() * d[:, 2].double() + perp2.double()).float() if exact else perp2 + par2
             i0 = torch.bucketize(d2, first2, right=True)
             j0 = b2 - (par2[:, None] < second2[None, :] * d2[:, None]).sum(1)
         else:
@@ -252,6 +271,8 @@ def pairs2d_bench(a, p: torch.Tensor, q: torch.Tensor, per: dict) -> int:
     second = [(1.0 if a.smu else R) * (j + 1) / b2 for j in range(b2)]
     Renc = R if a.smu else math.sqrt(2.0) * R * (1.0 + 1e-6)
     fn2d = E.pair_counts_smu if a.smu else E.pair_counts_rppi
+    obs = a.observer if a.los == "midpoint" else None
+    los = {} if obs is None else {"los": "midpoint", "observer": obs}
     index = E.build_index(p)
     first2 = torch.tensor([E.cut2_of(v) for v in first], device=p.device)
     second2 = torch.tensor([E.cut2_of(v) for v in second], device=p.device)
@@ -259,10 +280,12 @@ def pairs2d_bench(a, p: torch.Tensor, q: torch.Tensor, per: dict) -> int:
     chunk = max(1, int((1 << (24 if a.smu else 26)) / max(mean, 1.0)))
     out = {}
     cases = {
-        "pairs2d": lambda **kw: out.__setitem__("pairs2d", fn2d(index, q, first, second, **per, **kw)),
+        "pairs2d": lambda **kw: out.__setitem__("pairs2d", fn2d(index, q, first, second, **los, **per, **kw)),
         "pairs1d": lambda **kw: out.__setitem__(
             "pairs1d", E.pair_counts(index, q, [Renc * (i + 1) / b1 for i in range(b1)], **per, **kw)),
     }
+    if obs is not None:
+        cases["pairs2d_axis"] = lambda **kw: out.__setitem__("pairs2d_axis", fn2d(index, q, first, second, **kw))
     wts = None
     if a.weights:
         g = torch.Generator(device=p.device).manual_seed(5)
@@ -272,10 +295,14 @@ def pairs2d_bench(a, p: torch.Tensor, q: torch.Tensor, per: dict) -> int:
         pw = E.prepare_point_weights(index, w)
         wfn2d = E.weighted_pair_sums_smu if a.smu else E.weighted_pair_sums_rppi
         cases["wpairs2d"] = lambda **kw: out.__setitem__(
-            "wpairs2d", wfn2d(index, q, first, second, pw, query_weights=wq, **per, **kw))
+            "wpairs2d", wfn2d(index, q, first, second, pw, query_weights=wq, **los, **per, **kw))
+        if obs is not None:
+            cases["wpairs2d_axis"] = lambda **kw: out.__setitem__(
+                "wpairs2d_axis", wfn2d(index, q, first, second, pw, query_weights=wq, **kw))
     if not a.skip_pair_list:
         cases["pair_list"] = lambda: out.__setitem__(
-            "list", pair_list_cells(index, p, q, Renc, first2, second2, a.smu, per, a.period, chunk, wts))
+            "list", pair_list_cells(index, p, q, Renc, first2, second2, a.smu, per, a.period, chunk, wts,
+                                    observer=obs))
     times = {name: [] for name in cases}
     for step in range(a.warmup + a.steps):
         for name, fn in cases.items():
@@ -306,6 +333,14 @@ def pairs2d_bench(a, p: torch.Tensor, q: torch.Tensor, per: dict) -> int:
         "spread": {name: [min(ts), max(ts)] for name, ts in times.items()}, "counters": counters,
     }
     ok = True
+    if obs is not None:
+        rec.update({"los": "midpoint", "observer": list(obs), "pairs2d_axis_s": med["pairs2d_axis"],
+                    "observer_over_axis": med["pairs2d"] / med["pairs2d_axis"],
+                    "observer_over_axis_evals": counters["pairs2d"]["radius_evals"] /
+                    max(counters["pairs2d_axis"]["radius_evals"], 1)})
+        if a.weights:
+            rec.update({"wpairs2d_axis_s": med["wpairs2d_axis"],
+                        "weighted_observer_over_axis": med["wpairs2d"] / med["wpairs2d_axis"]})
     if a.weights:
         assert counters["wpairs2d"] == counters["pairs2d"], (counters["wpairs2d"], counters["pairs2d"])
         rec.update({"weights": "int64 +-2^15, query weights +-2^2", "wpairs2d_s": med["wpairs2d"],
@@ -315,14 +350,15 @@ def pairs2d_bench(a, p: torch.Tensor, q: torch.Tensor, per: dict) -> int:
             rec["pair_list_over_weighted"] = med["pair_list"] / med["wpairs2d"]
     if "list" in out:
         counted = out["list"] if wts is None else \
-            pair_list_cells(index, p, q, Renc, first2, second2, a.smu, per, a.period, chunk)
+            pair_list_cells(index, p, q, Renc, first2, second2, a.smu, per, a.period, chunk, observer=obs)
         moved = E.shell_counts_2d(S) != counted
         rec["pair_list_chunk"] = chunk
         rec["pair_list_cells_differing"] = int(moved.sum())
         rec["pair_list_total"] = int(counted.sum())
         if wts is not None:
             rec["weighted_pair_list_cells_differing"] = int((E.shell_counts_2d(out["wpairs2d"]) != out["list"]).sum())
-            fma = pair_list_cells(index, p, q, Renc, first2, second2, a.smu, per, a.period, chunk, wts, exact=True)
+            fma = pair_list_cells(index, p, q, Renc, first2, second2, a.smu, per, a.period, chunk, wts, exact=True,
+                                  observer=obs)
             ok = bool(torch.equal(E.shell_counts_2d(out["wpairs2d"]), fma))
             rec["weighted_equals_pair_list"] = ok
     if a.period is not None:
@@ -349,10 +385,19 @@ def main() -> int:
     ap.add_argument("--pairs-2d", default=None, metavar="BPxBL", help="time the anisotropic pair counts instead")
     ap.add_argument("--smu", action="store_true", help="--pairs-2d: the (s, mu) mode")
     ap.add_argument("--skip-pair-list", action="store_true", help="--pairs-2d: without the pair-list route")
+    ap.add_argument("--los", type=str.lower, choices=["z", "midpoint"], default="z",
+                    help="--pairs-2d: the line of sight, the z axis or from --observer to each pair's midpoint")
+    ap.add_argument("--observer", type=lambda t: tuple(float(v) for v in t.split(",")), default=None,
+                    metavar="ox,oy,oz", help="--los midpoint: the observer (default 0.5,0.5,-3)")
     add_period_option(ap)
     a = ap.parse_args()
     if a.pairs_2d is None and (a.smu or a.skip_pair_list):
         ap.error("--smu and --skip-pair-list belong to --pairs-2d")
+    if (a.los == "midpoint" and (a.pairs_2d is None or a.period is not None)) or \
+            (a.observer is not None and a.los != "midpoint"):
+        ap.error("--los midpoint belongs to --pairs-2d without --period, --observer to --los midpoint")
+    if a.los == "midpoint" and a.observer is None:
+        a.observer = (0.5, 0.5, -3.0)
     if a.profile < 0 or (a.profile == 0 and a.pairs_2d is None and
                          (a.radius is not None or a.self_queries or a.weights)):
         ap.error("--profile B needs B >= 1; -r, --self-queries and --weights belong to it")
