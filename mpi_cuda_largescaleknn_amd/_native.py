@@ -158,15 +158,8 @@ def _declare_host(lib: C.CDLL) -> None:
     lib.lsk_cpu_radius_profile.restype = None
     lib.lsk_cpu_weighted_profile.argtypes = [vp, i64, vp, i64, vp, i32, vp, vp, vp, i32]
     lib.lsk_cpu_weighted_profile.restype = None
-    lib.lsk_cpu_pair_counts_2d.argtypes = [vp, i64, vp, i64, vp, i32, vp, i32, i32, i32, vp, vp, i32]
-    lib.lsk_cpu_pair_counts_2d.restype = None
-    lib.lsk_cpu_weighted_pair_sums_2d.argtypes = [vp, i64, vp, i64, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, i32]
-    lib.lsk_cpu_weighted_pair_sums_2d.restype = None
-    lib.lsk_cpu_pair_counts_2d_observer.argtypes = [vp, i64, vp, i64, vp, i32, vp, i32, i32, vp, vp, i32]
-    lib.lsk_cpu_pair_counts_2d_observer.restype = None
-    lib.lsk_cpu_weighted_pair_sums_2d_observer.argtypes = [vp, i64, vp, i64, vp, i32, vp, i32, i32, vp, vp, vp, vp,
-                                                           i32]
-    lib.lsk_cpu_weighted_pair_sums_2d_observer.restype = None
+    lib.lsk_cpu_pair_sums_2d.argtypes = [vp, i64, vp, i64, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32]
+    lib.lsk_cpu_pair_sums_2d.restype = None
     lib.lsk_cpu_kth_periodic.argtypes = [vp, i64, vp, i64, i32, C.c_float, vp, vp, i32]
     lib.lsk_cpu_kth_periodic.restype = None
     lib.lsk_cpu_knn_periodic.argtypes = [vp, i64, vp, i64, i32, C.c_float, vp, vp, vp, i32]
@@ -252,14 +245,8 @@ def _declare_hip(lib: C.CDLL) -> None:
         "lsk_hip_weighted_pair_sums": ([C.POINTER(TreeView), vp, i64, vp, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp,
                                         vp], i32),
         "lsk_hip_pair_counts_2d_cells": ([], i32),
-        "lsk_hip_pair_counts_2d": ([C.POINTER(TreeView), vp, i64, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp],
-                                   i32),
-        "lsk_hip_weighted_pair_sums_2d": ([C.POINTER(TreeView), vp, i64, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp,
-                                           vp, vp, vp, vp], i32),
-        "lsk_hip_pair_counts_2d_observer": ([C.POINTER(TreeView), vp, i64, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp,
-                                             vp, vp], i32),
-        "lsk_hip_weighted_pair_sums_2d_observer": ([C.POINTER(TreeView), vp, i64, vp, vp, i32, vp, vp, i32, i32, vp,
-                                                    vp, vp, vp, vp, vp, vp, vp], i32),
+        "lsk_hip_pair_sums_2d": ([C.POINTER(TreeView), vp, i64, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp,
+                                  vp, vp, vp, vp], i32),
         "lsk_hip_pknn_flag": ([C.POINTER(TreeView), vp, vp, i64, C.c_float, vp, vp, vp, vp], i32),
         "lsk_hip_pknn_count": ([C.POINTER(TreeView), vp, vp, i64, vp, vp, vp, vp, vp], i32),
         "lsk_hip_pknn_fill": ([C.POINTER(TreeView), vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp], i32),

@@ -226,13 +226,8 @@ def pcheck(a) -> int:
         print(f"size mismatch: {got.shape[0]} cells for {a2.shape[0]} x {b2.shape[0]} edges")
         return 1
     got = got.view(a2.shape[0], b2.shape[0])
-    if isinstance(los, tuple):  # --los midpoint: the observer
-        ref = K.weighted_pair_sums_2d_observer_cpu(pts, qry, a2, b2, w, a.mode, los, query_weights=wq) if weighted \
-            else K.pair_counts_2d_observer_cpu(pts, qry, a2, b2, a.mode, los)
-    elif weighted:
-        ref = K.weighted_pair_sums_2d_cpu(pts, qry, a2, b2, w, a.mode, los, per, query_weights=wq)
-    else:
-        ref = K.pair_counts_2d_cpu(pts, qry, a2, b2, a.mode, los, per)
+    ref = K._pairs2d_cpu("pcheck", pts, qry, a2, b2, a.mode, los, per, (w, wq) if weighted else None,
+                         observer=isinstance(los, tuple))  # (a tuple: the observer of --los midpoint)
     wrong = (got != ref).nonzero()
     print(f"checked {ref.numel()} cells: {wrong.shape[0]} mismatches")
     for i, j in wrong[:10].tolist():

@@ -587,58 +587,46 @@ int run_pairs_2d(const char *what, typename WalkArgs<Policy, kObserver>::type &A
 
 extern "C" int lsk_hip_pair_counts_2d_cells(void) { return kCells; }
 
-extern "C" int lsk_hip_pair_counts_2d(const lsk_tree_view *tree, const float *qpts, int64_t nq, const float *a2,
-                                      int32_t na, const float *b2, int32_t nb, int32_t mode, int32_t los,
-                                      const float *period, const uint32_t *out_perm, int64_t *out,
-                                      unsigned long long *stats, void *stream) {
-  Pair2dArgs A{};
-  return run_pairs_2d<CountPolicy>("pair_counts_2d", A, tree, qpts, nq, a2, na, b2, nb, mode, los, period, out_perm,
-                                   out, stats, stream);
-}
-
-extern "C" int lsk_hip_weighted_pair_sums_2d(const lsk_tree_view *tree, const float *qpts, int64_t nq,
-                                             const float *a2, int32_t na, const float *b2, int32_t nb,
-                                             int32_t mode, int32_t los, const float *period,
-                                             const uint32_t *out_perm, const int64_t *wsorted, const int64_t *wpre,
-                                             const int64_t *wq, int64_t *out, unsigned long long *stats,
-                                             void *stream) {
-  if (nq > 0 && (!wsorted || !wpre)) {
-    lsk::set_last_error("weighted_pair_sums_2d: null argument");
+// The one entry point (lsk_hip.h states the null rules): the policy from the weights, the walk from
+// observer / period, `what` the name of that combination in error texts.
+extern "C" int lsk_hip_pair_sums_2d(const lsk_tree_view *tree, const float *qpts, int64_t nq, const float *a2,
+                                    const float *a2_host, int32_t na, const float *b2, const float *b2_host,
+                                    int32_t nb, int32_t mode, int32_t los, const float *period,
+                                    const float *observer, const uint32_t *out_perm, const int64_t *wsorted,
+                                    const int64_t *wpre, const int64_t *wq, int64_t *out,
+                                    unsigned long long *stats, void *stream) {
+  const bool weighted = wsorted || wpre;
+  const std::string what = std::string(weighted ? "weighted_pair_sums_2d" : "pair_counts_2d") +
+                           (observer ? "_observer" : "");
+  if (wq && !weighted) {
+    lsk::set_last_error(what + ": query weights (wq) without point weights (wsorted, wpre)");
     return 1;
   }
-  WeightedPair2dArgs A{};
-  A.wsorted = wsorted;
-  A.wpre = wpre;
-  A.wq = wq;
-  return run_pairs_2d<WeightPolicy>("weighted_pair_sums_2d", A, tree, qpts, nq, a2, na, b2, nb, mode, los, period,
-                                    out_perm, out, stats, stream);
-}
-
-extern "C" int lsk_hip_pair_counts_2d_observer(const lsk_tree_view *tree, const float *qpts, int64_t nq,
-                                               const float *a2, const float *a2_host, int32_t na, const float *b2,
-                                               const float *b2_host, int32_t nb, int32_t mode,
-                                               const float *observer, const uint32_t *out_perm, int64_t *out,
-                                               unsigned long long *stats, void *stream) {
-  ObserverArgs<Pair2dArgs> A{};
-  return run_pairs_2d<CountPolicy, true>("pair_counts_2d_observer", A, tree, qpts, nq, a2, na, b2, nb, mode, 0,
-                                         nullptr, out_perm, out, stats, stream, observer, a2_host, b2_host);
-}
-
-extern "C" int lsk_hip_weighted_pair_sums_2d_observer(const lsk_tree_view *tree, const float *qpts, int64_t nq,
-                                                      const float *a2, const float *a2_host, int32_t na,
-                                                      const float *b2, const float *b2_host, int32_t nb,
-                                                      int32_t mode, const float *observer,
-                                                      const uint32_t *out_perm, const int64_t *wsorted,
-                                                      const int64_t *wpre, const int64_t *wq, int64_t *out,
-                                                      unsigned long long *stats, void *stream) {
-  if (nq > 0 && (!wsorted || !wpre)) {
-    lsk::set_last_error("weighted_pair_sums_2d_observer: null argument");
+  if (observer && period) {
+    lsk::set_last_error(what + ": an observer line of sight takes no period (open box only)");
     return 1;
   }
-  ObserverArgs<WeightedPair2dArgs> A{};
-  A.wsorted = wsorted;
-  A.wpre = wpre;
-  A.wq = wq;
-  return run_pairs_2d<WeightPolicy, true>("weighted_pair_sums_2d_observer", A, tree, qpts, nq, a2, na, b2, nb, mode,
-                                          0, nullptr, out_perm, out, stats, stream, observer, a2_host, b2_host);
+  if (observer && (!a2_host || !b2_host)) {
+    lsk::set_last_error(what + ": an observer line of sight needs the host copies a2_host and b2_host");
+    return 1;
+  }
+  if (weighted && nq > 0 && (!wsorted || !wpre)) {
+    lsk::set_last_error(what + ": null argument");
+    return 1;
+  }
+  auto run = [&](auto policy, auto A) {
+    using Policy = decltype(policy);
+    constexpr bool kObserver = !std::is_same<decltype(A), typename Policy::args>::value;
+    if constexpr (std::is_same<Policy, WeightPolicy>::value) {
+      A.wsorted = wsorted;
+      A.wpre = wpre;
+      A.wq = wq;
+    }
+    return run_pairs_2d<Policy, kObserver>(what.c_str(), A, tree, qpts, nq, a2, na, b2, nb, mode, observer ? 0 : los,
+                                           period, out_perm, out, stats, stream, observer, a2_host, b2_host);
+  };
+  if (weighted)
+    return observer ? run(WeightPolicy{}, ObserverArgs<WeightedPair2dArgs>{})
+                    : run(WeightPolicy{}, WeightedPair2dArgs{});
+  return observer ? run(CountPolicy{}, ObserverArgs<Pair2dArgs>{}) : run(CountPolicy{}, Pair2dArgs{});
 }

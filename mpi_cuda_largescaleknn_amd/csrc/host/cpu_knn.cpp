@@ -537,14 +537,16 @@ extern "C" void lsk_cpu_weighted_profile(const float *pts, int64_t n, const floa
 // j0 = #{j : !(par2 < b2[j])}; mode 1, (s, mu): i0 = #{i : !(d2 < a2[i])}, j0 = #{j : !(par2 <
 // b2[j] * d2)} (one float32 product). A pair with i0 == na or j0 == nb is dropped. Every thread
 // counts differential cells of its own; out [na, nb] is the 2-D prefix sum of their total.
-// w (with wq: optional) null: every pair adds 1; else wq[q] * w[i] (wq null: w[i]), wrapping.
-// obs (open box; los and period unused): the line of sight of each pair is the direction from the
+// w (with wq: optional) null: every pair adds 1; else wq[q] * w[i] (wq null: w[i]), wrapping 64-bit
+// sums and products: exact whenever the true sums fit (the caller's check).
+// obs (open box: period null, los unused): the line of sight of each pair is the direction from the
 // observer obs[0 .. 3) to its midpoint. With l = (q - o) + (p - o) per axis, sl = fmaf(dz, lz,
 // fmaf(dy, ly, dx * lx)) and ll = dist2(l): par2 = (sl / ll) * sl, perp2 = d2 - par2 clamped at 0
 // from below (a NaN stays a NaN), d2 as before; the cells are the same.
-static void pair_sums_2d(const float *pts, int64_t n, const float *qry, int64_t nq, const float *a2, int32_t na,
-                         const float *b2, int32_t nb, int mode, int los, const float *period, const int64_t *w,
-                         const int64_t *wq, int64_t *out, int nthreads, const float *obs = nullptr) {
+extern "C" void lsk_cpu_pair_sums_2d(const float *pts, int64_t n, const float *qry, int64_t nq, const float *a2,
+                                     int32_t na, const float *b2, int32_t nb, int mode, int los, const float *period,
+                                     const float *obs, const int64_t *w, const int64_t *wq, int64_t *out,
+                                     int nthreads) {
   const vec3f *P = (const vec3f *)pts;
   const vec3f *Q = (const vec3f *)qry;
   if (na <= 0 || nb <= 0) return;
@@ -594,37 +596,6 @@ static void pair_sums_2d(const float *pts, int64_t n, const float *qry, int64_t 
       out[(size_t)i * nb + j] = (int64_t)(run + (i ? (uint64_t)out[(size_t)(i - 1) * nb + j] : 0));
     }
   }
-}
-
-extern "C" void lsk_cpu_pair_counts_2d(const float *pts, int64_t n, const float *qry, int64_t nq, const float *a2,
-                                       int32_t na, const float *b2, int32_t nb, int mode, int los,
-                                       const float *period, int64_t *out, int nthreads) {
-  pair_sums_2d(pts, n, qry, nq, a2, na, b2, nb, mode, los, period, nullptr, nullptr, out, nthreads);
-}
-
-// Weighted anisotropic pair sums: the brute force above with wq[q] * w[i] added to the pair's cell
-// in the place of 1 (wq null: all ones). Wrapping 64-bit sums and products: exact whenever the
-// true sums fit (the caller's check).
-extern "C" void lsk_cpu_weighted_pair_sums_2d(const float *pts, int64_t n, const float *qry, int64_t nq,
-                                              const float *a2, int32_t na, const float *b2, int32_t nb, int mode,
-                                              int los, const float *period, const int64_t *w, const int64_t *wq,
-                                              int64_t *out, int nthreads) {
-  pair_sums_2d(pts, n, qry, nq, a2, na, b2, nb, mode, los, period, w, wq, out, nthreads);
-}
-
-// The two above with the line of sight of an observer (three finite floats) in the place of an
-// axis: open box, pair_sums_2d with obs.
-extern "C" void lsk_cpu_pair_counts_2d_observer(const float *pts, int64_t n, const float *qry, int64_t nq,
-                                                const float *a2, int32_t na, const float *b2, int32_t nb, int mode,
-                                                const float *observer, int64_t *out, int nthreads) {
-  pair_sums_2d(pts, n, qry, nq, a2, na, b2, nb, mode, 0, nullptr, nullptr, nullptr, out, nthreads, observer);
-}
-
-extern "C" void lsk_cpu_weighted_pair_sums_2d_observer(const float *pts, int64_t n, const float *qry, int64_t nq,
-                                                       const float *a2, int32_t na, const float *b2, int32_t nb,
-                                                       int mode, const float *observer, const int64_t *w,
-                                                       const int64_t *wq, int64_t *out, int nthreads) {
-  pair_sums_2d(pts, n, qry, nq, a2, na, b2, nb, mode, 0, nullptr, w, wq, out, nthreads, observer);
 }
 
 // lsk_cpu_kth_brute under a period: the k-th smallest pdist2 among those < cut2, else cut2.

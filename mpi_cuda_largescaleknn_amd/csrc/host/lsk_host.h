@@ -141,32 +141,24 @@ void lsk_cpu_radius_profile(const float *pts, int64_t n, const float *qry, int64
 // Sums wrap in 64 bits: exact when sum |w| < 2^63.
 void lsk_cpu_weighted_profile(const float *pts, int64_t n, const float *qry, int64_t nq, const float *cut2s,
                               int32_t nb, const float *period, const int64_t *w, int64_t *out, int nthreads);
-// Anisotropic pair counts by brute force over all pairs: out (int64 [na, nb]) is cumulative on both
-// axes. los in {0, 1, 2} picks the line-of-sight difference dl of q - p (period: its minimum
-// image); par2 = dl * dl, perp2 = fmaf(db, db, da * da) of the other two axes in ascending order.
-// mode 0: out[i, j] = #{pairs : perp2 < a2[i] and par2 < b2[j]}; mode 1: #{pairs : d2 < a2[i] and
-// par2 < b2[j] * d2}. a2 / b2: na, nb >= 1 ascending values >= 0, +inf allowed, no NaN.
-void lsk_cpu_pair_counts_2d(const float *pts, int64_t n, const float *qry, int64_t nq, const float *a2, int32_t na,
-                            const float *b2, int32_t nb, int mode, int los, const float *period, int64_t *out,
-                            int nthreads);
-// The same with wq[q] * w[i] added per pair in the place of 1 (w: int64 [n]; wq: int64 [nq] or null
-// = all ones; negative allowed): the weighted anisotropic pair sums. Sums and products wrap in 64
-// bits: exact when (sum |w|) * (sum |wq|) < 2^63. With unit weights the counts above.
-void lsk_cpu_weighted_pair_sums_2d(const float *pts, int64_t n, const float *qry, int64_t nq, const float *a2,
-                                   int32_t na, const float *b2, int32_t nb, int mode, int los, const float *period,
-                                   const int64_t *w, const int64_t *wq, int64_t *out, int nthreads);
-// The two above in the open box with the line of sight of an observer (three finite floats) in the
-// place of an axis: per pair l = (q - o) + (p - o) per axis (twice observer -> midpoint), sl =
-// fmaf(dz, lz, fmaf(dy, ly, dx * lx)), ll = dist2(l), par2 = (sl / ll) * sl, perp2 = d2 - par2, a
-// negative perp2 becoming 0 and a NaN staying one; the same cells. A pair whose midpoint is the
-// observer (ll == 0) counts nowhere.
-void lsk_cpu_pair_counts_2d_observer(const float *pts, int64_t n, const float *qry, int64_t nq, const float *a2,
-                                     int32_t na, const float *b2, int32_t nb, int mode, const float *observer,
-                                     int64_t *out, int nthreads);
-void lsk_cpu_weighted_pair_sums_2d_observer(const float *pts, int64_t n, const float *qry, int64_t nq,
-                                            const float *a2, int32_t na, const float *b2, int32_t nb, int mode,
-                                            const float *observer, const int64_t *w, const int64_t *wq,
-                                            int64_t *out, int nthreads);
+// Anisotropic pair counts and weighted pair sums by brute force over all pairs: out (int64 [na, nb])
+// is cumulative on both axes. los in {0, 1, 2} picks the line-of-sight difference dl of q - p
+// (period: its minimum image); par2 = dl * dl, perp2 = fmaf(db, db, da * da) of the other two axes
+// in ascending order. mode 0: out[i, j] = #{pairs : perp2 < a2[i] and par2 < b2[j]}; mode 1: #{pairs
+// : d2 < a2[i] and par2 < b2[j] * d2}. a2 / b2: na, nb >= 1 ascending values >= 0, +inf allowed, no
+// NaN. What is null:
+//  * period: the open box.
+//  * w (int64 [n]): counts, every pair adds 1. Else wq[q] * w[i] is added per pair (wq: int64 [nq] or
+//    null = all ones; negative allowed; wq without w is ignored). Sums and products wrap in 64 bits:
+//    exact when (sum |w|) * (sum |wq|) < 2^63. With unit weights the counts.
+//  * observer: the axis los. Else (open box: period null, los unused) the line of sight of an
+//    observer (three finite floats): per pair l = (q - o) + (p - o) per axis (twice observer ->
+//    midpoint), sl = fmaf(dz, lz, fmaf(dy, ly, dx * lx)), ll = dist2(l), par2 = (sl / ll) * sl, perp2
+//    = d2 - par2, a negative perp2 becoming 0 and a NaN staying one; the same cells. A pair whose
+//    midpoint is the observer (ll == 0) counts nowhere.
+void lsk_cpu_pair_sums_2d(const float *pts, int64_t n, const float *qry, int64_t nq, const float *a2, int32_t na,
+                          const float *b2, int32_t nb, int mode, int los, const float *period,
+                          const float *observer, const int64_t *w, const int64_t *wq, int64_t *out, int nthreads);
 // lsk_cpu_kth_brute / lsk_cpu_knn_brute under a period: brute force over all points with the
 // periodic squared distance above, the same selection (k-th smallest by bits among those <
 // cut2, else cut2) and the same tie rule (ascending (d² bits, row); unfilled: -1 / cut2).

@@ -194,28 +194,29 @@ static void test_weighted_pair_sums_2d() {
   for (int mode : {0, 1})
     for (const float *period : {(const float *)nullptr, per})
       for (int los : {0, 1, 2}) {
-        lsk_cpu_pair_counts_2d(p.data(), n, q.data(), nq, a2, na, b2, nb, mode, los, period, c.data(), 3);
-        lsk_cpu_weighted_pair_sums_2d(p.data(), n, q.data(), nq, a2, na, b2, nb, mode, los, period, one.data(),
-                                      nullptr, s.data(), 3);
+        lsk_cpu_pair_sums_2d(p.data(), n, q.data(), nq, a2, na, b2, nb, mode, los, period, nullptr, nullptr, nullptr,
+                             c.data(), 3);
+        lsk_cpu_pair_sums_2d(p.data(), n, q.data(), nq, a2, na, b2, nb, mode, los, period, nullptr, one.data(),
+                             nullptr, s.data(), 3);
         CHECK(c == s);
       }
   // (rp, pi), open box, los = 2: every pair is below the last cutoffs (perp2 <= 2 needs a2 = 4)
   const float all_a[1] = {4.f}, all_b[1] = {INFINITY};
   int64_t got = 0, sw = 0, sq = 0;
-  lsk_cpu_weighted_pair_sums_2d(p.data(), n, q.data(), nq, all_a, 1, all_b, 1, 0, 2, nullptr, w.data(), wq.data(),
-                                &got, 2);
+  lsk_cpu_pair_sums_2d(p.data(), n, q.data(), nq, all_a, 1, all_b, 1, 0, 2, nullptr, nullptr, w.data(), wq.data(),
+                       &got, 2);
   for (auto x : w) sw += x;
   for (auto x : wq) sq += x;
   CHECK(got == sw * sq);
-  lsk_cpu_weighted_pair_sums_2d(p.data(), n, q.data(), nq, all_a, 1, all_b, 1, 0, 2, nullptr, w.data(), nullptr,
-                                &got, 2);
+  lsk_cpu_pair_sums_2d(p.data(), n, q.data(), nq, all_a, 1, all_b, 1, 0, 2, nullptr, nullptr, w.data(), nullptr,
+                       &got, 2);
   CHECK(got == sw * nq);
   // three points on the z axis, one query at the origin: par2 = 0.01, 0.09, 0.25, perp2 = 0
   const float pz[9] = {0, 0, 0.1f, 0, 0, 0.3f, 0, 0, 0.5f}, q0[3] = {0, 0, 0};
   const int64_t w3[3] = {5, -7, 11}, wq1[1] = {-3};
   const float ea[1] = {1.f}, eb[3] = {0.04f, 0.16f, 1.f};
   int64_t r3[3];
-  lsk_cpu_weighted_pair_sums_2d(pz, 3, q0, 1, ea, 1, eb, 3, 0, 2, nullptr, w3, wq1, r3, 1);
+  lsk_cpu_pair_sums_2d(pz, 3, q0, 1, ea, 1, eb, 3, 0, 2, nullptr, nullptr, w3, wq1, r3, 1);
   CHECK(r3[0] == -15 && r3[1] == 6 && r3[2] == -27);
 }
 

@@ -1013,8 +1013,7 @@ def _periodic_knn(index: LocalIndex, per: tuple, cfg: KnnConfig, qsorted: torch.
                             cfg.cut2, cfg.k, out, out_idx, out_dist, err)
         LAST_PERIODIC_KNN_ERRORS[0] = int(err.item()) & 0xFFFFFFFF
     if stats is not None:
-        for nm, v in zip(_RADIUS_PERIODIC_STATS, raw.cpu().tolist()):
-            stats.counters[nm] = stats.counters.get(nm, 0) + int(v)
+        _add_stats(stats, _RADIUS_PERIODIC_STATS, raw)
         stats.counters["periodic_flagged"] = stats.counters.get("periodic_flagged", 0) + qlist.numel()
         stats.counters["periodic_pairs"] = stats.counters.get("periodic_pairs", 0) + pairs
     if LAST_PERIODIC_KNN_ERRORS[0]:
@@ -1188,8 +1187,11 @@ def _radius_cut2(what: str, radius: float, squared: bool = False) -> float:
 _RADIUS_STATS = ("radius_evals", "radius_nodes", "radius_buckets", "radius_box_accepts")
 
 
-def _add_radius_stats(stats: KnnStats, raw: torch.Tensor) -> None:
-    for nm, v in zip(_RADIUS_STATS, raw.cpu().tolist()):
+def _add_stats(stats: KnnStats | None, names: tuple, raw: torch.Tensor | None) -> None:
+    """Add the words of a kernel's raw stats tensor to stats.counters under `names` (no stats: nothing)."""
+    if stats is None:
+        return
+    for nm, v in zip(names, raw.cpu().tolist()):
         stats.counters[nm] = stats.counters.get(nm, 0) + int(v)
 
 
@@ -1276,8 +1278,7 @@ def _var_counts(what: str, index: LocalIndex, queries: torch.Tensor, qcut2: torc
         tree = (index.pts, prad.nodes, index.qnodes, n, index.depth)
         counts = K.radius_var_count_gpu(tree, qsorted, nq, qperm, pcut2=prad.cut2_sorted, stats=raw)
     KERNELS_USED.add("radius_var")
-    if stats is not None:
-        _add_radius_stats(stats, raw)
+    _add_stats(stats, _RADIUS_STATS, raw)
     return counts
 
 
@@ -1396,9 +1397,7 @@ def _periodic_counts(index: LocalIndex, queries: torch.Tensor, cut2: float, qcut
     raw = torch.zeros(K.RADIUS_PERIODIC_STATS, dtype=torch.int64, device=index.device) if stats is not None else None
     counts = K.radius_periodic_count_gpu(index.tree(), qsorted, nq, cut2, qperm, per, qcut2=qcut2, stats=raw)
     KERNELS_USED.add("radius_periodic")
-    if stats is not None:
-        for nm, v in zip(_RADIUS_PERIODIC_STATS, raw.cpu().tolist()):
-            stats.counters[nm] = stats.counters.get(nm, 0) + int(v)
+    _add_stats(stats, _RADIUS_PERIODIC_STATS, raw)
     return counts
 
 
@@ -1474,9 +1473,7 @@ def radius_counts(index: LocalIndex, queries: torch.Tensor, radius: float | torc
     raw = torch.zeros(4, dtype=torch.int64, device=index.device) if stats is not None else None
     counts = K.radius_count_gpu(index.tree(), qsorted, nq, cut2, qperm, stats=raw)
     KERNELS_USED.add("radius")
-    if stats is not None:
-        for nm, v in zip(_RADIUS_STATS, raw.cpu().tolist()):
-            stats.counters[nm] = stats.counters.get(nm, 0) + int(v)
+    _add_stats(stats, _RADIUS_STATS, raw)
     return counts
 
 
@@ -1604,28 +1601,46 @@ def _profile_cutoffs(what: str, radii, squared: bool, period) -> tuple:
 
 
 def _profile(what: str, index: LocalIndex, queries: torch.Tensor, radii, squared: bool, period,
-             stats: KnnStats | None, sums: bool) -> torch.Tensor:
+             stats: KnnStats | None, sums: bool, weights: tuple | None = None) -> torch.Tensor:
+    """The runner of the radius profiles. sums: the [B] sums over the queries in the place of the [nq,
+    B] profile; weights: None = the counts, else (point weights, query weights or None) of the
+    weighted forms (query weights belong to the sums alone)."""
     cut2s, per = _profile_cutoffs(what, radii, squared, period)
     if index.qrot is not None or index.line:
         raise ValueError(f"{what}: an index built in a rotated frame or sorted by line keys is not supported")
     queries = _check_foreign(what, index, queries)
     nq, n, nb = queries.shape[0], index.n, cut2s.shape[0]
-    if nq == 0 or n == 0:
+    pw = wq = None
+    if weights is not None:
+        pw = _point_weights(what, index, weights[0])
         if sums:
-            return torch.zeros(nb, dtype=torch.int64, device=index.device)
-        return torch.zeros((nq, nb), dtype=torch.int32, device=index.device)
+            if weights[1] is not None:
+                wq = K.int64_weights(what, "query_weights", weights[1], nq, index.device)
+            check_pair_sum_bound(what, pw, wq, nq)
+    if nq == 0 or n == 0:
+        return torch.zeros(nb if sums else (nq, nb), dtype=torch.int64 if sums or weights is not None else torch.int32,
+                           device=index.device)
     if not K.is_gpu(index.pts):
         KERNELS_USED.add("cpu")
-        return (K.pair_counts_cpu if sums else K.radius_profile_cpu)(index.pts[:n], queries, cut2s, per)
+        if weights is None:
+            return (K.pair_counts_cpu if sums else K.radius_profile_cpu)(index.pts[:n], queries, cut2s, per)
+        if sums:
+            return K.weighted_pair_sums_cpu(index.pts[:n], queries, cut2s, pw.sorted, per, query_weights=wq)
+        return K.weighted_profile_cpu(index.pts[:n], queries, cut2s, pw.sorted, per)
     qsorted, qperm = prepare_queries(index, queries, locate=False)[:2]
     names = _RADIUS_STATS if per is None else _RADIUS_PERIODIC_STATS
     raw = torch.zeros(len(names), dtype=torch.int64, device=index.device) if stats is not None else None
-    out = (K.pair_counts_gpu if sums else K.radius_profile_gpu)(index.tree(), qsorted, nq, cut2s, qperm, per,
-                                                                stats=raw)
-    KERNELS_USED.add("radius_profile")
-    if stats is not None:
-        for nm, v in zip(names, raw.cpu().tolist()):
-            stats.counters[nm] = stats.counters.get(nm, 0) + int(v)
+    if weights is None:
+        out = (K.pair_counts_gpu if sums else K.radius_profile_gpu)(index.tree(), qsorted, nq, cut2s, qperm, per,
+                                                                    stats=raw)
+    elif sums:
+        out = K.weighted_pair_sums_gpu(index.tree(), qsorted, nq, cut2s, qperm, pw.sorted, pw.prefix,
+                                       query_weights=wq, period=per, stats=raw)
+    else:
+        out = K.weighted_profile_gpu(index.tree(), qsorted, nq, cut2s, qperm, pw.sorted, pw.prefix, period=per,
+                                     stats=raw)
+    KERNELS_USED.add("radius_profile" if weights is None else "weighted_profile")
+    _add_stats(stats, names, raw)
     return out
 
 
@@ -1663,14 +1678,19 @@ def pair_counts(index: LocalIndex, queries: torch.Tensor, radii, squared: bool =
     return _profile("pair_counts", index, queries, radii, squared, period, stats, True)
 
 
-def _profile_index(what: str, points: torch.Tensor, queries: torch.Tensor, radii, squared: bool,
-                   period) -> LocalIndex | None:
-    """The index of the *_query_* / *_self_* profile forms; None when there is nothing to index
-    (the radii are checked all the same)."""
+def _profile_index(what: str, points: torch.Tensor, queries: torch.Tensor, radii, squared: bool, period,
+                   weights: tuple | None = None) -> LocalIndex | None:
+    """The index of the *_query_* / *_self_* profile forms; None when there is nothing to index (the
+    radii, and the (point weights, query weights or None) of a weighted form, are checked all the
+    same)."""
     if points.device != queries.device:
         raise ValueError(f"{what}: points on {points.device}, queries on {queries.device}")
     if points.shape[0] == 0:
         _profile_cutoffs(what, radii, squared, period)
+        if weights is not None:
+            K.int64_weights(what, "weights", weights[0], 0, points.device)
+            if weights[1] is not None:
+                K.int64_weights(what, "query_weights", weights[1], queries.shape[0], queries.device)
         return None
     return build_index(points)
 
@@ -1778,45 +1798,54 @@ def _pairs2d_cutoffs(what: str, mode: str, first, second, los, squared: bool, pe
 
 
 def _pairs2d(what: str, mode: str, index: LocalIndex, queries: torch.Tensor, first, second, los, squared: bool,
-             period, stats: KnnStats | None, observer=None) -> torch.Tensor:
+             period, stats: KnnStats | None, observer=None, weights: tuple | None = None) -> torch.Tensor:
+    """The runner of the anisotropic pair statistics. weights: None = the counts, else (point weights,
+    query weights or None) of the weighted sums."""
     a2, b2, los, per = _pairs2d_cutoffs(what, mode, first, second, los, squared, period, observer)
     midpoint = isinstance(los, tuple)  # the observer itself
     if index.qrot is not None or index.line:
         raise ValueError(f"{what}: an index built in a rotated frame or sorted by line keys is not supported")
     queries = _check_foreign(what, index, queries)
     nq, n = queries.shape[0], index.n
+    pw = wq = None
+    if weights is not None:
+        pw = _point_weights(what, index, weights[0])
+        if weights[1] is not None:
+            wq = K.int64_weights(what, "query_weights", weights[1], nq, index.device)
+        check_pair_sum_bound(what, pw, wq, nq)
     if nq == 0 or n == 0:
         return torch.zeros((a2.shape[0], b2.shape[0]), dtype=torch.int64, device=index.device)
     if not K.is_gpu(index.pts):
         KERNELS_USED.add("cpu")
-        if midpoint:
-            return K.pair_counts_2d_observer_cpu(index.pts[:n], queries, a2, b2, mode, los)
-        return K.pair_counts_2d_cpu(index.pts[:n], queries, a2, b2, mode, los, per)
+        return K._pairs2d_cpu(what, index.pts[:n], queries, a2, b2, mode, los, per,
+                              None if pw is None else (pw.sorted, wq), observer=midpoint)
     qsorted, qperm = prepare_queries(index, queries, locate=False)[:2]
     names = _RADIUS_STATS if per is None else _RADIUS_PERIODIC_STATS
     raw = torch.zeros(len(names), dtype=torch.int64, device=index.device) if stats is not None else None
-    if midpoint:
-        out = K.pair_counts_2d_observer_gpu(index.tree(), qsorted, nq, a2, b2, mode, los, qperm, stats=raw)
-        KERNELS_USED.add("pair_counts_2d_observer")
-    else:
-        out = K.pair_counts_2d_gpu(index.tree(), qsorted, nq, a2, b2, mode, los, qperm, per, stats=raw)
-        KERNELS_USED.add("pair_counts_2d")
-    if stats is not None:
-        for nm, v in zip(names, raw.cpu().tolist()):
-            stats.counters[nm] = stats.counters.get(nm, 0) + int(v)
+    out = K.pair_sums_2d_gpu(index.tree(), qsorted, nq, a2, b2, mode, los, qperm, per,
+                             None if pw is None else (pw.sorted, pw.prefix), wq, stats=raw)
+    KERNELS_USED.add(("pair_counts_2d" if pw is None else "weighted_pair_sums_2d") + ("_observer" if midpoint else ""))
+    _add_stats(stats, names, raw)
     return out
 
 
-def _pairs2d_index(what: str, mode: str, points: torch.Tensor, queries: torch.Tensor, first, second, los,
-                   squared: bool, period, observer=None) -> tuple:
-    """(index or None, the empty result) of the *_query_* / *_self_* forms (the arguments are
-    checked all the same when there is nothing to index)."""
+def _pairs2d_points(what: str, inner: str, mode: str, points: torch.Tensor, queries: torch.Tensor, first, second,
+                    los, squared: bool, period, stats: KnnStats | None, observer=None,
+                    weights: tuple | None = None) -> torch.Tensor:
+    """The *_query_* / *_self_* forms: _pairs2d over an index built once from `points` (the arguments
+    are checked all the same when there is nothing to index). inner: the name in the errors raised
+    once there is an index (the count forms report those under their index form's name)."""
     if points.device != queries.device:
         raise ValueError(f"{what}: points on {points.device}, queries on {queries.device}")
     a2, b2 = _pairs2d_cutoffs(what, mode, first, second, los, squared, period, observer)[:2]  # (before the index)
     if points.shape[0] == 0:
-        return None, torch.zeros((a2.shape[0], b2.shape[0]), dtype=torch.int64, device=queries.device)
-    return build_index(points), None
+        if weights is not None:
+            K.int64_weights(what, "weights", weights[0], 0, points.device)
+            if weights[1] is not None:
+                K.int64_weights(what, "query_weights", weights[1], queries.shape[0], queries.device)
+        return torch.zeros((a2.shape[0], b2.shape[0]), dtype=torch.int64, device=queries.device)
+    return _pairs2d(inner, mode, build_index(points), queries, first, second, los, squared, period, stats, observer,
+                    weights)
 
 
 def pair_counts_rppi(index: LocalIndex, queries: torch.Tensor, rp, pi, los=2, squared: bool = False, period=None,
@@ -1862,12 +1891,8 @@ def pair_counts_rppi(index: LocalIndex, queries: torch.Tensor, rp, pi, los=2, sq
 def pair_query_counts_rppi(points: torch.Tensor, queries: torch.Tensor, rp, pi, los=2, squared: bool = False,
                            period=None, stats: KnnStats | None = None, observer=None) -> torch.Tensor:
     """pair_counts_rppi over an index built once from `points`, in the points' own frame."""
-    index, empty = _pairs2d_index("pair_query_counts_rppi", "rppi", points, queries, rp, pi, los, squared, period,
-                                  observer)
-    if index is None:
-        return empty
-    return pair_counts_rppi(index, queries, rp, pi, los=los, squared=squared, period=period, stats=stats,
-                            observer=observer)
+    return _pairs2d_points("pair_query_counts_rppi", "pair_counts_rppi", "rppi", points, queries, rp, pi, los, squared,
+                           period, stats, observer)
 
 
 def pair_self_counts_rppi(points: torch.Tensor, rp, pi, los=2, squared: bool = False, period=None,
@@ -1899,12 +1924,8 @@ def pair_counts_smu(index: LocalIndex, queries: torch.Tensor, s, mu, los=2, squa
 def pair_query_counts_smu(points: torch.Tensor, queries: torch.Tensor, s, mu, los=2, squared: bool = False,
                           period=None, stats: KnnStats | None = None, observer=None) -> torch.Tensor:
     """pair_counts_smu over an index built once from `points`, in the points' own frame."""
-    index, empty = _pairs2d_index("pair_query_counts_smu", "smu", points, queries, s, mu, los, squared, period,
-                                  observer)
-    if index is None:
-        return empty
-    return pair_counts_smu(index, queries, s, mu, los=los, squared=squared, period=period, stats=stats,
-                           observer=observer)
+    return _pairs2d_points("pair_query_counts_smu", "pair_counts_smu", "smu", points, queries, s, mu, los, squared,
+                           period, stats, observer)
 
 
 def pair_self_counts_smu(points: torch.Tensor, s, mu, los=2, squared: bool = False, period=None,
@@ -2006,44 +2027,6 @@ def _point_weights(what: str, index: LocalIndex, weights) -> PointWeights:
         raise ValueError(str(e).replace("prepare_point_weights", what, 1)) from None
 
 
-def _weighted(what: str, index: LocalIndex, queries: torch.Tensor, radii, weights, query_weights, squared: bool,
-              period, stats: KnnStats | None, sums: bool) -> torch.Tensor:
-    cut2s, per = _profile_cutoffs(what, radii, squared, period)
-    if index.qrot is not None or index.line:
-        raise ValueError(f"{what}: an index built in a rotated frame or sorted by line keys is not supported")
-    queries = _check_foreign(what, index, queries)
-    nq, n, nb = queries.shape[0], index.n, cut2s.shape[0]
-    pw = _point_weights(what, index, weights)
-    wq = None
-    if sums:
-        if query_weights is not None:
-            wq = K.int64_weights(what, "query_weights", query_weights, nq, index.device)
-        check_pair_sum_bound(what, pw, wq, nq)
-    if nq == 0 or n == 0:
-        if sums:
-            return torch.zeros(nb, dtype=torch.int64, device=index.device)
-        return torch.zeros((nq, nb), dtype=torch.int64, device=index.device)
-    if not K.is_gpu(index.pts):
-        KERNELS_USED.add("cpu")
-        if sums:
-            return K.weighted_pair_sums_cpu(index.pts[:n], queries, cut2s, pw.sorted, per, query_weights=wq)
-        return K.weighted_profile_cpu(index.pts[:n], queries, cut2s, pw.sorted, per)
-    qsorted, qperm = prepare_queries(index, queries, locate=False)[:2]
-    names = _RADIUS_STATS if per is None else _RADIUS_PERIODIC_STATS
-    raw = torch.zeros(len(names), dtype=torch.int64, device=index.device) if stats is not None else None
-    if sums:
-        out = K.weighted_pair_sums_gpu(index.tree(), qsorted, nq, cut2s, qperm, pw.sorted, pw.prefix,
-                                       query_weights=wq, period=per, stats=raw)
-    else:
-        out = K.weighted_profile_gpu(index.tree(), qsorted, nq, cut2s, qperm, pw.sorted, pw.prefix, period=per,
-                                     stats=raw)
-    KERNELS_USED.add("weighted_profile")
-    if stats is not None:
-        for nm, v in zip(names, raw.cpu().tolist()):
-            stats.counters[nm] = stats.counters.get(nm, 0) + int(v)
-    return out
-
-
 def weighted_profile(index: LocalIndex, queries: torch.Tensor, radii, weights, squared: bool = False, period=None,
                      stats: KnnStats | None = None) -> torch.Tensor:
     """int64 [nq, B], in query order: WP[q, b] = the sum of weights[p] over the points of `index`
@@ -2063,7 +2046,7 @@ def weighted_profile(index: LocalIndex, queries: torch.Tensor, radii, weights, s
     built in a rotated frame or sorted by line keys is not supported. `stats` receives the
     radius_* counters of radius_profile (the two walks visit the same nodes). More radii than
     the kernel's slice width (16) are served in slices, one walk each."""
-    return _weighted("weighted_profile", index, queries, radii, weights, None, squared, period, stats, False)
+    return _profile("weighted_profile", index, queries, radii, squared, period, stats, False, (weights, None))
 
 
 def weighted_pair_sums(index: LocalIndex, queries: torch.Tensor, radii, weights, query_weights=None,
@@ -2076,25 +2059,15 @@ def weighted_pair_sums(index: LocalIndex, queries: torch.Tensor, radii, weights,
     query weights) must be below 2^63, checked on the host: every partial sum is then exact.
     Integer sums: two runs give the same bits. With unit weights this is pair_counts. Other
     arguments and errors as for weighted_profile."""
-    return _weighted("weighted_pair_sums", index, queries, radii, weights, query_weights, squared, period, stats,
-                     True)
-
-
-def _weighted_index(what: str, points: torch.Tensor, queries: torch.Tensor, radii, weights, squared: bool,
-                    period) -> LocalIndex | None:
-    """The index of the *_query_* / *_self_* weighted forms; None when there is nothing to index
-    (the radii and the weights are checked all the same)."""
-    index = _profile_index(what, points, queries, radii, squared, period)
-    if index is None:
-        K.int64_weights(what, "weights", weights, 0, points.device)
-    return index
+    return _profile("weighted_pair_sums", index, queries, radii, squared, period, stats, True,
+                    (weights, query_weights))
 
 
 def weighted_query_profile(points: torch.Tensor, queries: torch.Tensor, radii, weights: torch.Tensor,
                            squared: bool = False, period=None, stats: KnnStats | None = None) -> torch.Tensor:
     """weighted_profile over an index built once from `points` (both float32 [*, 3] on one
     device), in the points' own frame; weights: int64 [n], one per row of `points`."""
-    index = _weighted_index("weighted_query_profile", points, queries, radii, weights, squared, period)
+    index = _profile_index("weighted_query_profile", points, queries, radii, squared, period, (weights, None))
     if index is None:
         return torch.zeros((queries.shape[0], len(radii)), dtype=torch.int64, device=queries.device)
     return weighted_profile(index, queries, radii, weights, squared=squared, period=period, stats=stats)
@@ -2111,11 +2084,9 @@ def weighted_pair_query_sums(points: torch.Tensor, queries: torch.Tensor, radii,
                              query_weights: torch.Tensor | None = None, squared: bool = False, period=None,
                              stats: KnnStats | None = None) -> torch.Tensor:
     """weighted_pair_sums over an index built once from `points`, in the points' own frame."""
-    index = _weighted_index("weighted_pair_query_sums", points, queries, radii, weights, squared, period)
+    index = _profile_index("weighted_pair_query_sums", points, queries, radii, squared, period,
+                           (weights, query_weights))
     if index is None:
-        if query_weights is not None:
-            K.int64_weights("weighted_pair_query_sums", "query_weights", query_weights, queries.shape[0],
-                           queries.device)
         return torch.zeros(len(radii), dtype=torch.int64, device=queries.device)
     return weighted_pair_sums(index, queries, radii, weights, query_weights=query_weights, squared=squared,
                               period=period, stats=stats)
@@ -2135,61 +2106,6 @@ def weighted_pair_self_sums(points: torch.Tensor, radii, weights: torch.Tensor,
 
 
 # ---- weighted anisotropic pair sums: weights on DD(rp, pi) and DD(s, mu) (pair_counts_2d.hip)
-def _weighted_pairs2d(what: str, mode: str, index: LocalIndex, queries: torch.Tensor, first, second, weights,
-                      query_weights, los, squared: bool, period, stats: KnnStats | None,
-                      observer=None) -> torch.Tensor:
-    a2, b2, los, per = _pairs2d_cutoffs(what, mode, first, second, los, squared, period, observer)
-    midpoint = isinstance(los, tuple)  # the observer itself
-    if index.qrot is not None or index.line:
-        raise ValueError(f"{what}: an index built in a rotated frame or sorted by line keys is not supported")
-    queries = _check_foreign(what, index, queries)
-    nq, n = queries.shape[0], index.n
-    pw = _point_weights(what, index, weights)
-    wq = None
-    if query_weights is not None:
-        wq = K.int64_weights(what, "query_weights", query_weights, nq, index.device)
-    check_pair_sum_bound(what, pw, wq, nq)
-    if nq == 0 or n == 0:
-        return torch.zeros((a2.shape[0], b2.shape[0]), dtype=torch.int64, device=index.device)
-    if not K.is_gpu(index.pts):
-        KERNELS_USED.add("cpu")
-        if midpoint:
-            return K.weighted_pair_sums_2d_observer_cpu(index.pts[:n], queries, a2, b2, pw.sorted, mode, los,
-                                                        query_weights=wq)
-        return K.weighted_pair_sums_2d_cpu(index.pts[:n], queries, a2, b2, pw.sorted, mode, los, per,
-                                           query_weights=wq)
-    qsorted, qperm = prepare_queries(index, queries, locate=False)[:2]
-    names = _RADIUS_STATS if per is None else _RADIUS_PERIODIC_STATS
-    raw = torch.zeros(len(names), dtype=torch.int64, device=index.device) if stats is not None else None
-    if midpoint:
-        out = K.weighted_pair_sums_2d_observer_gpu(index.tree(), qsorted, nq, a2, b2, mode, los, qperm, pw.sorted,
-                                                   pw.prefix, query_weights=wq, stats=raw)
-        KERNELS_USED.add("weighted_pair_sums_2d_observer")
-    else:
-        out = K.weighted_pair_sums_2d_gpu(index.tree(), qsorted, nq, a2, b2, mode, los, qperm, pw.sorted, pw.prefix,
-                                          period=per, query_weights=wq, stats=raw)
-        KERNELS_USED.add("weighted_pair_sums_2d")
-    if stats is not None:
-        for nm, v in zip(names, raw.cpu().tolist()):
-            stats.counters[nm] = stats.counters.get(nm, 0) + int(v)
-    return out
-
-
-def _weighted_pairs2d_points(what: str, mode: str, points: torch.Tensor, queries: torch.Tensor, first, second,
-                             weights, query_weights, los, squared: bool, period,
-                             stats: KnnStats | None, observer=None) -> torch.Tensor:
-    """The *_query_* / *_self_* forms: an index built once from `points` (the arguments are checked
-    all the same when there is nothing to index)."""
-    index, empty = _pairs2d_index(what, mode, points, queries, first, second, los, squared, period, observer)
-    if index is None:
-        K.int64_weights(what, "weights", weights, 0, points.device)
-        if query_weights is not None:
-            K.int64_weights(what, "query_weights", query_weights, queries.shape[0], queries.device)
-        return empty
-    return _weighted_pairs2d(what, mode, index, queries, first, second, weights, query_weights, los, squared,
-                             period, stats, observer)
-
-
 def weighted_pair_sums_rppi(index: LocalIndex, queries: torch.Tensor, rp, pi, weights, query_weights=None, los=2,
                             squared: bool = False, period=None, stats: KnnStats | None = None,
                             observer=None) -> torch.Tensor:
@@ -2212,16 +2128,16 @@ def weighted_pair_sums_rppi(index: LocalIndex, queries: torch.Tensor, rp, pi, we
     another index, either bound exceeded and every argument error of pair_counts_rppi raise
     ValueError; an index built in a rotated frame or sorted by line keys is not supported. `stats`
     receives the radius_* counters. los='midpoint' and observer as for pair_counts_rppi."""
-    return _weighted_pairs2d("weighted_pair_sums_rppi", "rppi", index, queries, rp, pi, weights, query_weights, los,
-                             squared, period, stats, observer)
+    return _pairs2d("weighted_pair_sums_rppi", "rppi", index, queries, rp, pi, los, squared, period, stats, observer,
+                    (weights, query_weights))
 
 
 def weighted_pair_query_sums_rppi(points: torch.Tensor, queries: torch.Tensor, rp, pi, weights: torch.Tensor,
                                   query_weights: torch.Tensor | None = None, los=2, squared: bool = False,
                                   period=None, stats: KnnStats | None = None, observer=None) -> torch.Tensor:
     """weighted_pair_sums_rppi over an index built once from `points`, in the points' own frame."""
-    return _weighted_pairs2d_points("weighted_pair_query_sums_rppi", "rppi", points, queries, rp, pi, weights,
-                                    query_weights, los, squared, period, stats, observer)
+    return _pairs2d_points("weighted_pair_query_sums_rppi", "weighted_pair_query_sums_rppi", "rppi", points, queries,
+                           rp, pi, los, squared, period, stats, observer, (weights, query_weights))
 
 
 def weighted_pair_self_sums_rppi(points: torch.Tensor, rp, pi, weights: torch.Tensor,
@@ -2231,9 +2147,9 @@ def weighted_pair_self_sums_rppi(points: torch.Tensor, rp, pi, weights: torch.Te
     is given, `weights` on both sides: ordered pairs, (p, q) and (q, p) both, and every finite point
     with itself (perp2 = par2 = 0: w[p]^2 in every cell with cutoffs > 0), like
     weighted_pair_self_sums."""
-    return _weighted_pairs2d_points("weighted_pair_self_sums_rppi", "rppi", points, points, rp, pi, weights,
-                                    weights if query_weights is None else query_weights, los, squared, period,
-                                    stats, observer)
+    return _pairs2d_points("weighted_pair_self_sums_rppi", "weighted_pair_self_sums_rppi", "rppi", points, points, rp,
+                           pi, los, squared, period, stats, observer,
+                           (weights, weights if query_weights is None else query_weights))
 
 
 def weighted_pair_sums_smu(index: LocalIndex, queries: torch.Tensor, s, mu, weights, query_weights=None, los=2,
@@ -2244,16 +2160,16 @@ def weighted_pair_sums_smu(index: LocalIndex, queries: torch.Tensor, s, mu, weig
     weighted_pair_sums_rppi is pair_counts_rppi with weights. A pair with d2 == 0 adds to no cell;
     there is no whole-box acceptance in this mode. s, mu and everything else as for
     pair_counts_smu, weights and errors as for weighted_pair_sums_rppi."""
-    return _weighted_pairs2d("weighted_pair_sums_smu", "smu", index, queries, s, mu, weights, query_weights, los,
-                             squared, period, stats, observer)
+    return _pairs2d("weighted_pair_sums_smu", "smu", index, queries, s, mu, los, squared, period, stats, observer,
+                    (weights, query_weights))
 
 
 def weighted_pair_query_sums_smu(points: torch.Tensor, queries: torch.Tensor, s, mu, weights: torch.Tensor,
                                  query_weights: torch.Tensor | None = None, los=2, squared: bool = False,
                                  period=None, stats: KnnStats | None = None, observer=None) -> torch.Tensor:
     """weighted_pair_sums_smu over an index built once from `points`, in the points' own frame."""
-    return _weighted_pairs2d_points("weighted_pair_query_sums_smu", "smu", points, queries, s, mu, weights,
-                                    query_weights, los, squared, period, stats, observer)
+    return _pairs2d_points("weighted_pair_query_sums_smu", "weighted_pair_query_sums_smu", "smu", points, queries,
+                           s, mu, los, squared, period, stats, observer, (weights, query_weights))
 
 
 def weighted_pair_self_sums_smu(points: torch.Tensor, s, mu, weights: torch.Tensor,
@@ -2261,9 +2177,9 @@ def weighted_pair_self_sums_smu(points: torch.Tensor, s, mu, weights: torch.Tens
                                 period=None, stats: KnnStats | None = None, observer=None) -> torch.Tensor:
     """weighted_pair_query_sums_smu with the points as their own queries and, unless query_weights is
     given, `weights` on both sides: ordered pairs; a point with itself (d2 == 0) adds nowhere."""
-    return _weighted_pairs2d_points("weighted_pair_self_sums_smu", "smu", points, points, s, mu, weights,
-                                    weights if query_weights is None else query_weights, los, squared, period,
-                                    stats, observer)
+    return _pairs2d_points("weighted_pair_self_sums_smu", "weighted_pair_self_sums_smu", "smu", points, points, s,
+                           mu, los, squared, period, stats, observer,
+                           (weights, weights if query_weights is None else query_weights))
 
 
 def fixed_point_weights(weights: torch.Tensor, n_terms: int | None = None, bits: int = 62) -> tuple:
@@ -2420,11 +2336,8 @@ def _cluster_periodic(index: LocalIndex, cut2: float, min_pts: int, per: tuple,
     if LAST_CLUSTER_ERRORS[0]:
         raise NativeError(f"cluster_labels: {LAST_CLUSTER_ERRORS[0]} parent chains did not end "
                           "(the union-find's invariant is broken: a bug)")
-    if stats is not None:
-        for nm, v in zip(_RADIUS_PERIODIC_STATS, raw_r.cpu().tolist()):
-            stats.counters[nm] = stats.counters.get(nm, 0) + int(v)
-        for nm, v in zip(_CLUSTER_STATS, raw_c.cpu().tolist()):
-            stats.counters[nm] = stats.counters.get(nm, 0) + int(v)
+    _add_stats(stats, _RADIUS_PERIODIC_STATS, raw_r)
+    _add_stats(stats, _CLUSTER_STATS, raw_c)
     return labels, core
 
 
@@ -2482,10 +2395,8 @@ def cluster_labels(index: LocalIndex, eps: float, min_pts: int = 1, squared: boo
     if LAST_CLUSTER_ERRORS[0]:
         raise NativeError(f"cluster_labels: {LAST_CLUSTER_ERRORS[0]} parent chains did not end "
                           "(the union-find's invariant is broken: a bug)")
-    if stats is not None:
-        _add_radius_stats(stats, raw_r)
-        for nm, v in zip(_CLUSTER_STATS, raw_c.cpu().tolist()):
-            stats.counters[nm] = stats.counters.get(nm, 0) + int(v)
+    _add_stats(stats, _RADIUS_STATS, raw_r)
+    _add_stats(stats, _CLUSTER_STATS, raw_c)
     return labels, core
 
 
@@ -2680,8 +2591,7 @@ def mst_edges(index: LocalIndex, core_d2: torch.Tensor | None = None,
     if done != want:
         raise NativeError(f"mst_edges: {done} edges for {n_finite} finite points (a bug)")
     if stats is not None:
-        for nm, v in zip(_MST_STATS, raw.cpu().tolist()):
-            stats.counters[nm] = stats.counters.get(nm, 0) + int(v)
+        _add_stats(stats, _MST_STATS, raw)
         stats.counters["mst_rounds"] = rounds
         stats.counters["mst_components"] = comps
     rows, d2 = state.rows[:want], state.d2[:want]

@@ -1209,6 +1209,13 @@ def _profile_stats(what: str, stats: torch.Tensor | None, period, dev: torch.dev
         raise ValueError(f"{what}: stats int64 [{need}] on the tree's device")
 
 
+def _query_weights_arg(what: str, wq: torch.Tensor | None, nq: int, dev: torch.device) -> torch.Tensor | None:
+    if wq is not None and (wq.dtype != torch.int64 or wq.dim() != 1 or wq.shape[0] != nq or not wq.is_contiguous()
+                           or wq.device != dev):
+        raise ValueError(f"{what}: query_weights must be a contiguous int64 [{nq}] tensor on the tree's device")
+    return wq
+
+
 def _profile_slices(name: str, tree: tuple, qsorted: torch.Tensor, nq: int, cut2s, out_perm: torch.Tensor, period,
                     stats: torch.Tensor | None, sums: bool, weights: tuple | None = None,
                     query_weights: torch.Tensor | None = None) -> torch.Tensor:
@@ -1222,10 +1229,7 @@ def _profile_slices(name: str, tree: tuple, qsorted: torch.Tensor, nq: int, cut2
     _profile_stats(what, stats, period, dev)
     if weights is not None:
         _weighted_args(what, tree, *weights)
-    wq = query_weights
-    if wq is not None and (wq.dtype != torch.int64 or wq.dim() != 1 or wq.shape[0] != nq or not wq.is_contiguous()
-                           or wq.device != dev):
-        raise ValueError(f"{what}: query_weights must be a contiguous int64 [{nq}] tensor on the tree's device")
+    wq = _query_weights_arg(what, query_weights, nq, dev)
     nb = c.shape[0]
     lib = _native.hip()
     if sums:
@@ -1287,45 +1291,6 @@ def _pairs2d_args(what: str, a2, b2, mode: str, los: int) -> tuple:
     return a, b
 
 
-def pair_counts_2d_cpu(points: torch.Tensor, queries: torch.Tensor, a2, b2, mode: str, los: int = 2,
-                       period=None) -> torch.Tensor:
-    """CPU oracle (brute force over all pairs) of the anisotropic pair counts: int64 [Ba, Bb],
-    cumulative on both axes. mode 'rppi': S[i, j] = #{pairs : perp2 < a2[i] and par2 < b2[j]};
-    'smu': #{pairs : d2 < a2[i] and par2 < b2[j] * d2}, with par2 = dl * dl of the line-of-sight
-    axis `los` of the float32 differences q - p (period: their minimum image), perp2 = fmaf(db,
-    db, da * da) of the other two. a2 / b2: ascending squared cutoffs (sequences or CPU tensors)."""
-    a, b = _pairs2d_args("pair_counts_2d_cpu", a2, b2, mode, los)
-    per = None if period is None else check_period("pair_counts_2d_cpu", period)
-    pts = points.contiguous().float().cpu()
-    q = queries.contiguous().float().cpu()
-    out = torch.zeros((a.shape[0], b.shape[0]), dtype=torch.int64)
-    _native.host().lsk_cpu_pair_counts_2d(_ptr(pts), pts.shape[0], _ptr(q), q.shape[0], _ptr(a), a.shape[0], _ptr(b),
-                                          b.shape[0], PAIRS2D_MODES[mode], int(los),
-                                          None if per is None else _period_c(per), _ptr(out), _nthreads())
-    return out
-
-
-def pair_counts_2d_gpu(tree: tuple, qsorted: torch.Tensor, nq: int, a2, b2, mode: str, los: int,
-                       out_perm: torch.Tensor, period: tuple[float, float, float] | None = None,
-                       stats: torch.Tensor | None = None) -> torch.Tensor:
-    """The anisotropic pair counts (pair_counts_2d.hip) on the current stream: int64 [Ba, Bb] on the
-    tree's device, what pair_counts_2d_cpu defines, from one walk per slice of 2048 cells; the
-    blocks add their cells to the result, one small kernel makes it cumulative. tree / qsorted /
-    out_perm / period / stats as for pair_counts_gpu."""
-    what = "pair_counts_2d_gpu"
-    a, b = _pairs2d_args(what, a2, b2, mode, los)
-    tv = _walk_view(what, tree, qsorted, nq, out_perm)
-    dev = tree[0].device
-    _profile_stats(what, stats, period, dev)
-    res = torch.empty((a.shape[0], b.shape[0]), dtype=torch.int64, device=dev)
-    adev, bdev = a.to(dev), b.to(dev)
-    check(_native.hip().lsk_hip_pair_counts_2d(C.byref(tv), _ptr(qsorted), int(nq), _ptr(adev), a.shape[0],
-                                               _ptr(bdev), b.shape[0], PAIRS2D_MODES[mode], int(los),
-                                               None if period is None else _period_c(period), _ptr(out_perm),
-                                               _ptr(res), _ptr(stats), _stream(tree[0])), "pair_counts_2d")
-    return res
-
-
 def check_observer(what: str, observer) -> tuple[float, float, float]:
     """(ox, oy, oz) as float32 values, each finite. Anything else raises ValueError."""
     if isinstance(observer, torch.Tensor):
@@ -1339,6 +1304,76 @@ def check_observer(what: str, observer) -> tuple[float, float, float]:
     return vals
 
 
+def _pairs2d_cpu(what: str, points: torch.Tensor, queries: torch.Tensor, a2, b2, mode: str, los, period=None,
+                 weights: tuple | None = None, observer: bool = False) -> torch.Tensor:
+    """The body of the four oracles below: the checks under the caller's name, then one call of
+    lsk_cpu_pair_sums_2d. observer: `los` holds the observer, not an axis (open box: no period);
+    weights: None = the counts, else (weights, query_weights or None)."""
+    a, b = _pairs2d_args(what, a2, b2, mode, 0 if observer else los)
+    obs = check_observer(what, los) if observer else None
+    per = None if period is None else check_period(what, period)
+    pts = points.contiguous().float().cpu()
+    q = queries.contiguous().float().cpu()
+    w = wq = None
+    if weights is not None:
+        w = int64_weights(what, "weights", weights[0], pts.shape[0]).cpu()
+        if weights[1] is not None:
+            wq = int64_weights(what, "query_weights", weights[1], q.shape[0]).cpu()
+    out = torch.zeros((a.shape[0], b.shape[0]), dtype=torch.int64)
+    _native.host().lsk_cpu_pair_sums_2d(_ptr(pts), pts.shape[0], _ptr(q), q.shape[0], _ptr(a), a.shape[0], _ptr(b),
+                                        b.shape[0], PAIRS2D_MODES[mode], 0 if observer else int(los),
+                                        None if per is None else _period_c(per),
+                                        None if obs is None else _period_c(obs), _ptr(w), _ptr(wq), _ptr(out),
+                                        _nthreads())
+    return out
+
+
+def pair_sums_2d_gpu(tree: tuple, qsorted: torch.Tensor, nq: int, a2, b2, mode: str, los, out_perm: torch.Tensor,
+                     period: tuple[float, float, float] | None = None, weights: tuple | None = None,
+                     query_weights: torch.Tensor | None = None, stats: torch.Tensor | None = None) -> torch.Tensor:
+    """The anisotropic pair counts and weighted pair sums (pair_counts_2d.hip) on the current stream:
+    int64 [Ba, Bb] on the tree's device, what the four oracles below define, from one walk per slice
+    of 2048 cells; the blocks add their cells to the result, one small kernel makes it cumulative.
+    tree / qsorted / out_perm / period / stats as for pair_counts_gpu.
+    los: an axis (0, 1, 2), or the observer (three finite numbers): the observer walk, open box; its
+    cull is a ball per slice whose radius the library takes from the host copies of the cutoffs, and
+    there is no whole-box acceptance (word 3 of stats stays 0).
+    weights: None = the counts, else (wsorted, wprefix), int64 [n] / [n + 1], the weights in the
+    tree's curve order and their exclusive prefix sum; query_weights: int64 [nq] in query order or
+    None, with weights only. The caller guarantees max|w| * n < 2^62 and (sum |w|) * (sum
+    |query_weights|) < 2^63. The library refuses query weights without weights and an observer with
+    a period (NativeError) before it queues anything."""
+    what = "pair_sums_2d_gpu"
+    axis = isinstance(los, int)
+    a, b = _pairs2d_args(what, a2, b2, mode, los if axis else 0)
+    obs = None if axis else check_observer(what, los)
+    tv = _walk_view(what, tree, qsorted, nq, out_perm)
+    dev = tree[0].device
+    _profile_stats(what, stats, period, dev)
+    if weights is not None:
+        _weighted_args(what, tree, *weights)
+    wq = _query_weights_arg(what, query_weights, nq, dev)
+    res = torch.empty((a.shape[0], b.shape[0]), dtype=torch.int64, device=dev)
+    adev, bdev = a.to(dev), b.to(dev)
+    check(_native.hip().lsk_hip_pair_sums_2d(
+        C.byref(tv), _ptr(qsorted), int(nq), _ptr(adev), None if axis else _ptr(a), a.shape[0], _ptr(bdev),
+        None if axis else _ptr(b), b.shape[0], PAIRS2D_MODES[mode], int(los) if axis else 0,
+        None if period is None else _period_c(period), None if axis else _period_c(obs), _ptr(out_perm),
+        *(_ptr(t) for t in weights or (None, None)), _ptr(wq), _ptr(res), _ptr(stats), _stream(tree[0])),
+        "pair_sums_2d")
+    return res
+
+
+def pair_counts_2d_cpu(points: torch.Tensor, queries: torch.Tensor, a2, b2, mode: str, los: int = 2,
+                       period=None) -> torch.Tensor:
+    """CPU oracle (brute force over all pairs) of the anisotropic pair counts: int64 [Ba, Bb],
+    cumulative on both axes. mode 'rppi': S[i, j] = #{pairs : perp2 < a2[i] and par2 < b2[j]};
+    'smu': #{pairs : d2 < a2[i] and par2 < b2[j] * d2}, with par2 = dl * dl of the line-of-sight
+    axis `los` of the float32 differences q - p (period: their minimum image), perp2 = fmaf(db,
+    db, da * da) of the other two. a2 / b2: ascending squared cutoffs (sequences or CPU tensors)."""
+    return _pairs2d_cpu("pair_counts_2d_cpu", points, queries, a2, b2, mode, los, period)
+
+
 def pair_counts_2d_observer_cpu(points: torch.Tensor, queries: torch.Tensor, a2, b2, mode: str,
                                 observer=(0.0, 0.0, 0.0)) -> torch.Tensor:
     """CPU oracle (brute force over all pairs) of the anisotropic pair counts with the line of sight
@@ -1346,37 +1381,7 @@ def pair_counts_2d_observer_cpu(points: torch.Tensor, queries: torch.Tensor, a2,
     axis (twice the vector observer -> midpoint), sl = fmaf(dz, lz, fmaf(dy, ly, dx * lx)), ll =
     dist2(l), par2 = (sl / ll) * sl and perp2 = d2 - par2 (a negative one becomes 0, a NaN stays),
     all float32. A pair whose midpoint is the observer counts nowhere."""
-    what = "pair_counts_2d_observer_cpu"
-    a, b = _pairs2d_args(what, a2, b2, mode, 0)
-    obs = check_observer(what, observer)
-    pts = points.contiguous().float().cpu()
-    q = queries.contiguous().float().cpu()
-    out = torch.zeros((a.shape[0], b.shape[0]), dtype=torch.int64)
-    _native.host().lsk_cpu_pair_counts_2d_observer(_ptr(pts), pts.shape[0], _ptr(q), q.shape[0], _ptr(a), a.shape[0],
-                                                   _ptr(b), b.shape[0], PAIRS2D_MODES[mode], _period_c(obs),
-                                                   _ptr(out), _nthreads())
-    return out
-
-
-def pair_counts_2d_observer_gpu(tree: tuple, qsorted: torch.Tensor, nq: int, a2, b2, mode: str, observer,
-                                out_perm: torch.Tensor, stats: torch.Tensor | None = None) -> torch.Tensor:
-    """The observer walk of pair_counts_2d.hip on the current stream: int64 [Ba, Bb] on the tree's
-    device, what pair_counts_2d_observer_cpu defines. Open box; the cull is a ball per slice whose
-    radius the library takes from the host copies of the cutoffs; no whole-box acceptance (word 3
-    of stats stays 0). Everything else as for pair_counts_2d_gpu."""
-    what = "pair_counts_2d_observer_gpu"
-    a, b = _pairs2d_args(what, a2, b2, mode, 0)
-    obs = check_observer(what, observer)
-    tv = _walk_view(what, tree, qsorted, nq, out_perm)
-    dev = tree[0].device
-    _profile_stats(what, stats, None, dev)
-    res = torch.empty((a.shape[0], b.shape[0]), dtype=torch.int64, device=dev)
-    adev, bdev = a.to(dev), b.to(dev)
-    check(_native.hip().lsk_hip_pair_counts_2d_observer(
-        C.byref(tv), _ptr(qsorted), int(nq), _ptr(adev), _ptr(a), a.shape[0], _ptr(bdev), _ptr(b), b.shape[0],
-        PAIRS2D_MODES[mode], _period_c(obs), _ptr(out_perm), _ptr(res), _ptr(stats), _stream(tree[0])),
-        "pair_counts_2d_observer")
-    return res
+    return _pairs2d_cpu("pair_counts_2d_observer_cpu", points, queries, a2, b2, mode, observer, observer=True)
 
 
 # --------------------------------------------------------------------------- weighted radius profiles
@@ -1466,49 +1471,8 @@ def weighted_pair_sums_2d_cpu(points: torch.Tensor, queries: torch.Tensor, a2, b
     the place of 1. weights: int64 [n], one per row of `points`; query_weights: int64 [nq] or None
     (all ones); negative allowed. Sums and products wrap in 64 bits (exact when (sum |w|) * (sum
     |wq|) < 2^63). With unit weights this is pair_counts_2d_cpu."""
-    what = "weighted_pair_sums_2d_cpu"
-    a, b = _pairs2d_args(what, a2, b2, mode, los)
-    per = None if period is None else check_period(what, period)
-    pts = points.contiguous().float().cpu()
-    q = queries.contiguous().float().cpu()
-    w = int64_weights(what, "weights", weights, pts.shape[0]).cpu()
-    wq = None if query_weights is None else int64_weights(what, "query_weights", query_weights, q.shape[0]).cpu()
-    out = torch.zeros((a.shape[0], b.shape[0]), dtype=torch.int64)
-    _native.host().lsk_cpu_weighted_pair_sums_2d(_ptr(pts), pts.shape[0], _ptr(q), q.shape[0], _ptr(a), a.shape[0],
-                                                 _ptr(b), b.shape[0], PAIRS2D_MODES[mode], int(los),
-                                                 None if per is None else _period_c(per), _ptr(w), _ptr(wq),
-                                                 _ptr(out), _nthreads())
-    return out
-
-
-def weighted_pair_sums_2d_gpu(tree: tuple, qsorted: torch.Tensor, nq: int, a2, b2, mode: str, los: int,
-                              out_perm: torch.Tensor, wsorted: torch.Tensor, wprefix: torch.Tensor,
-                              period: tuple[float, float, float] | None = None,
-                              query_weights: torch.Tensor | None = None,
-                              stats: torch.Tensor | None = None) -> torch.Tensor:
-    """The weighted anisotropic pair sums (pair_counts_2d.hip, the weight policy) on the current
-    stream: int64 [Ba, Bb] on the tree's device, what weighted_pair_sums_2d_cpu defines, from the
-    walk of pair_counts_2d_gpu. wsorted / wprefix: int64 [n] / [n + 1], the weights in the tree's
-    curve order and their exclusive prefix sum; query_weights: int64 [nq] in query order or None.
-    The caller guarantees max|w| * n < 2^62 and (sum |w|) * (sum |query_weights|) < 2^63.
-    Everything else as for pair_counts_2d_gpu."""
-    what = "weighted_pair_sums_2d_gpu"
-    a, b = _pairs2d_args(what, a2, b2, mode, los)
-    tv = _walk_view(what, tree, qsorted, nq, out_perm)
-    dev = tree[0].device
-    _profile_stats(what, stats, period, dev)
-    _weighted_args(what, tree, wsorted, wprefix)
-    wq = query_weights
-    if wq is not None and (wq.dtype != torch.int64 or wq.dim() != 1 or wq.shape[0] != nq or not wq.is_contiguous()
-                           or wq.device != dev):
-        raise ValueError(f"{what}: query_weights must be a contiguous int64 [{nq}] tensor on the tree's device")
-    res = torch.empty((a.shape[0], b.shape[0]), dtype=torch.int64, device=dev)
-    adev, bdev = a.to(dev), b.to(dev)
-    check(_native.hip().lsk_hip_weighted_pair_sums_2d(
-        C.byref(tv), _ptr(qsorted), int(nq), _ptr(adev), a.shape[0], _ptr(bdev), b.shape[0], PAIRS2D_MODES[mode],
-        int(los), None if period is None else _period_c(period), _ptr(out_perm), _ptr(wsorted), _ptr(wprefix),
-        _ptr(wq), _ptr(res), _ptr(stats), _stream(tree[0])), "weighted_pair_sums_2d")
-    return res
+    return _pairs2d_cpu("weighted_pair_sums_2d_cpu", points, queries, a2, b2, mode, los, period,
+                        (weights, query_weights))
 
 
 def weighted_pair_sums_2d_observer_cpu(points: torch.Tensor, queries: torch.Tensor, a2, b2, weights: torch.Tensor,
@@ -1517,45 +1481,8 @@ def weighted_pair_sums_2d_observer_cpu(points: torch.Tensor, queries: torch.Tens
     """CPU oracle of the weighted anisotropic pair sums with the line of sight of an observer:
     pair_counts_2d_observer_cpu with query_weights[q] * weights[p] added per pair in the place of 1,
     weights and wrapping as for weighted_pair_sums_2d_cpu."""
-    what = "weighted_pair_sums_2d_observer_cpu"
-    a, b = _pairs2d_args(what, a2, b2, mode, 0)
-    obs = check_observer(what, observer)
-    pts = points.contiguous().float().cpu()
-    q = queries.contiguous().float().cpu()
-    w = int64_weights(what, "weights", weights, pts.shape[0]).cpu()
-    wq = None if query_weights is None else int64_weights(what, "query_weights", query_weights, q.shape[0]).cpu()
-    out = torch.zeros((a.shape[0], b.shape[0]), dtype=torch.int64)
-    _native.host().lsk_cpu_weighted_pair_sums_2d_observer(
-        _ptr(pts), pts.shape[0], _ptr(q), q.shape[0], _ptr(a), a.shape[0], _ptr(b), b.shape[0], PAIRS2D_MODES[mode],
-        _period_c(obs), _ptr(w), _ptr(wq), _ptr(out), _nthreads())
-    return out
-
-
-def weighted_pair_sums_2d_observer_gpu(tree: tuple, qsorted: torch.Tensor, nq: int, a2, b2, mode: str, observer,
-                                       out_perm: torch.Tensor, wsorted: torch.Tensor, wprefix: torch.Tensor,
-                                       query_weights: torch.Tensor | None = None,
-                                       stats: torch.Tensor | None = None) -> torch.Tensor:
-    """The observer walk of pair_counts_2d.hip under the weight policy: int64 [Ba, Bb] on the tree's
-    device, what weighted_pair_sums_2d_observer_cpu defines. Weights and their bounds as for
-    weighted_pair_sums_2d_gpu, everything else as for pair_counts_2d_observer_gpu."""
-    what = "weighted_pair_sums_2d_observer_gpu"
-    a, b = _pairs2d_args(what, a2, b2, mode, 0)
-    obs = check_observer(what, observer)
-    tv = _walk_view(what, tree, qsorted, nq, out_perm)
-    dev = tree[0].device
-    _profile_stats(what, stats, None, dev)
-    _weighted_args(what, tree, wsorted, wprefix)
-    wq = query_weights
-    if wq is not None and (wq.dtype != torch.int64 or wq.dim() != 1 or wq.shape[0] != nq or not wq.is_contiguous()
-                           or wq.device != dev):
-        raise ValueError(f"{what}: query_weights must be a contiguous int64 [{nq}] tensor on the tree's device")
-    res = torch.empty((a.shape[0], b.shape[0]), dtype=torch.int64, device=dev)
-    adev, bdev = a.to(dev), b.to(dev)
-    check(_native.hip().lsk_hip_weighted_pair_sums_2d_observer(
-        C.byref(tv), _ptr(qsorted), int(nq), _ptr(adev), _ptr(a), a.shape[0], _ptr(bdev), _ptr(b), b.shape[0],
-        PAIRS2D_MODES[mode], _period_c(obs), _ptr(out_perm), _ptr(wsorted), _ptr(wprefix), _ptr(wq), _ptr(res),
-        _ptr(stats), _stream(tree[0])), "weighted_pair_sums_2d_observer")
-    return res
+    return _pairs2d_cpu("weighted_pair_sums_2d_observer_cpu", points, queries, a2, b2, mode, observer,
+                        weights=(weights, query_weights), observer=True)
 
 
 # --------------------------------------------------------------------------- periodic k-NN

@@ -254,3 +254,104 @@ def test_every_mu_gives_pair_counts_without_the_zero_distances(name, period):
     zero = E.pair_counts(index, q, [2.0 ** -149], squared=True, period=period)[0]
     want = E.pair_counts(index, q, R, period=period) - zero
     assert int(zero) >= NQ // 2 and torch.equal(got[:, 0], want)
+
+
+# ---------------------------------------------------------------- 5. the one entry point
+def _entry_case():
+    """200 uniform points (four buckets, a tree of depth 2), 70 queries (one full group and one
+    partial), a 2 x 3 grid per mode; weights on both sides; everything the wrapper takes."""
+    def make():
+        g = torch.Generator().manual_seed(77)
+        p, q = torch.rand((200, 3), generator=g), torch.rand((70, 3), generator=g)
+        w = torch.randint(-9, 10, (200,), generator=g, dtype=torch.int64)
+        wq = torch.randint(-3, 4, (70,), generator=g, dtype=torch.int64)
+        index = E.build_index(p.to(DEV))
+        assert index.depth == 2
+        qsorted, qperm = E.prepare_queries(index, q.to(DEV), locate=False)[:2]
+        pw = E.prepare_point_weights(index, w.to(DEV))
+        edges = {"rppi": ([0.2, 0.4], [0.1, 0.25, 0.45]), "smu": ([0.2, 0.4], [0.3, 0.7, INF])}
+        cuts = {m: tuple([E.cut2_of(r) for r in e] for e in fs) for m, fs in edges.items()}
+        return p, q, w, wq, index, qsorted, qperm, pw, cuts
+    return cached("entry", make)
+
+
+OBSERVER = (0.5, 0.4, -2.0)
+
+
+def _entry_oracle(mode, los, period, weighted, with_wq):
+    p, q, w, wq, _, _, _, _, cuts = _entry_case()
+    a2, b2 = cuts[mode]
+    wq = wq if with_wq else None
+    if isinstance(los, tuple):
+        return K.weighted_pair_sums_2d_observer_cpu(p, q, a2, b2, w, mode, los, query_weights=wq) if weighted \
+            else K.pair_counts_2d_observer_cpu(p, q, a2, b2, mode, los)
+    return K.weighted_pair_sums_2d_cpu(p, q, a2, b2, w, mode, los, period, query_weights=wq) if weighted \
+        else K.pair_counts_2d_cpu(p, q, a2, b2, mode, los, period)
+
+
+def _entry_gpu(mode, los, period, weighted, with_wq):
+    _, q, _, wq, index, qsorted, qperm, pw, cuts = _entry_case()
+    return K.pair_sums_2d_gpu(index.tree(), qsorted, q.shape[0], *cuts[mode], mode, los, qperm, period,
+                              (pw.sorted, pw.prefix) if weighted else None, wq.to(DEV) if with_wq else None).cpu()
+
+
+_ENTRY_FORMS = ((False, False), (True, False), (True, True))  # (weights, query weights)
+_ENTRY_LOS = ((0, None), (1, ISO), (2, None), (2, (1.0, INF, 0.9)), (OBSERVER, None))
+
+
+@pytest.mark.parametrize("mode", ("rppi", "smu"))
+def test_one_entry_serves_every_combination(mode):
+    """K.pair_sums_2d_gpu once per valid combination of policy, line of sight and box: each result is
+    the corresponding oracle's, bit for bit."""
+    for weighted, with_wq in _ENTRY_FORMS:
+        for los, period in _ENTRY_LOS:
+            got = _entry_gpu(mode, los, period, weighted, with_wq)
+            want = _entry_oracle(mode, los, period, weighted, with_wq)
+            assert got.dtype == torch.int64 and torch.equal(got, want), (mode, weighted, with_wq, los, period)
+    assert int(_entry_oracle(mode, 2, None, False, False)[-1, -1]) > 0
+
+
+def test_one_entry_refuses_what_the_four_could_not_express():
+    """Query weights without point weights, an observer with a period, an observer without the host
+    copies of the cutoffs: each is refused in host code before anything is queued (the result
+    buffer keeps its filling), and the next valid call equals the oracle."""
+    from mpi_cuda_largescaleknn_amd import _native
+    _, q, _, wq, index, qsorted, qperm, pw, cuts = _entry_case()
+    nq, (a2, b2), tree = q.shape[0], cuts["rppi"], index.tree()
+    wqd = wq.to(DEV)
+    with pytest.raises(_native.NativeError, match="pair_counts_2d: .*wq"):
+        K.pair_sums_2d_gpu(tree, qsorted, nq, a2, b2, "rppi", 2, qperm, query_weights=wqd)
+    assert torch.equal(_entry_gpu("rppi", 2, None, False, False), _entry_oracle("rppi", 2, None, False, False))
+    with pytest.raises(_native.NativeError, match="weighted_pair_sums_2d_observer: .*period"):
+        K.pair_sums_2d_gpu(tree, qsorted, nq, a2, b2, "rppi", OBSERVER, qperm, ISO, (pw.sorted, pw.prefix), wqd)
+    assert torch.equal(_entry_gpu("rppi", OBSERVER, None, True, True),
+                       _entry_oracle("rppi", OBSERVER, None, True, True))
+
+    # the library itself: the wrapper always sends the host copies with an observer
+    import ctypes as C
+    a, b = torch.tensor(a2), torch.tensor(b2)
+    adev, bdev = a.to(DEV), b.to(DEV)
+    tv = _native.TreeView(tree[0].data_ptr(), tree[1].data_ptr(), tree[2].data_ptr(), tree[3], tree[4], 0)
+    obs, per = (C.c_float * 3)(*OBSERVER), (C.c_float * 3)(*ISO)
+    out = torch.full((2, 3), -7, dtype=torch.int64, device=DEV)
+    lib = _native.hip()
+
+    def call(a_host, b_host, period, observer, wsorted, wpre, wq_):
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        rc = lib.lsk_hip_pair_sums_2d(C.byref(tv), qsorted.data_ptr(), nq, adev.data_ptr(), ptr(a_host), 2,
+                                      bdev.data_ptr(), ptr(b_host), 3, 0, 2, period, observer, qperm.data_ptr(),
+                                      ptr(wsorted), ptr(wpre), ptr(wq_), out.data_ptr(), None,
+                                      torch.cuda.current_stream().cuda_stream)
+        return rc, lib.lsk_hip_last_error().decode()
+
+    for args, text in (((None, None, None, None, None, None, wqd), "pair_counts_2d: "),
+                       ((a, b, per, obs, None, None, None), "pair_counts_2d_observer: "),
+                       ((None, None, None, obs, pw.sorted, pw.prefix, None), "weighted_pair_sums_2d_observer: "),
+                       ((a, None, None, obs, None, None, None), "pair_counts_2d_observer: ")):
+        rc, msg = call(*args)
+        assert rc == 1 and msg.startswith(text), (rc, msg)
+        assert bool((out == -7).all())  # not even the zero fill was queued
+        assert torch.equal(_entry_gpu("rppi", 2, ISO, True, False), _entry_oracle("rppi", 2, ISO, True, False))
+    rc, msg = call(a, b, None, obs, None, None, None)  # the same call, complete
+    assert rc == 0, msg
+    assert torch.equal(out.cpu(), _entry_oracle("rppi", OBSERVER, None, False, False))
