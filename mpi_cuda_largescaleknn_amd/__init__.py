@@ -43,7 +43,8 @@ from .models.knn_engine import (KnnConfig, build_index, cluster_labels, cluster_
                                 point_radius_neighbors, point_radius_query_counts, point_radius_query_neighbors,
                                 point_radius_self_neighbors, prepare_point_radii, query, query_neighbors, query_points,
                                 radius_counts, radius_neighbors, radius_query_counts, radius_query_neighbors,
-                                radius_self_neighbors, radius_profile, radius_query_profile, radius_self_profile,
+                                radius_self_neighbors, reach_counts, reach_neighbors, reach_query_counts,
+                                reach_query_neighbors, reach_self_neighbors, radius_profile, radius_query_profile, radius_self_profile,
                                 pair_counts, pair_query_counts, pair_self_counts, PointWeights,
                                 prepare_point_weights, fixed_point_weights, weighted_profile, weighted_query_profile,
                                 weighted_self_profile, weighted_pair_sums, weighted_pair_query_sums,

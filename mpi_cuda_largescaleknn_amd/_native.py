@@ -154,6 +154,10 @@ def _declare_host(lib: C.CDLL) -> None:
     lib.lsk_cpu_radius_periodic_fill.restype = None
     lib.lsk_cpu_cluster_periodic.argtypes = [vp, i64, C.c_float, i32, vp, vp, vp, i32]
     lib.lsk_cpu_cluster_periodic.restype = None
+    lib.lsk_cpu_radius_reach_count.argtypes = [vp, i64, vp, i64, vp, vp, i32, vp, vp, i32]
+    lib.lsk_cpu_radius_reach_count.restype = None
+    lib.lsk_cpu_radius_reach_fill.argtypes = [vp, i64, vp, i64, vp, vp, i32, vp, vp, vp, vp, i32]
+    lib.lsk_cpu_radius_reach_fill.restype = None
     lib.lsk_cpu_radius_profile.argtypes = [vp, i64, vp, i64, vp, i32, vp, vp, i32]
     lib.lsk_cpu_radius_profile.restype = None
     lib.lsk_cpu_weighted_profile.argtypes = [vp, i64, vp, i64, vp, i32, vp, vp, vp, i32]
@@ -234,6 +238,9 @@ def _declare_hip(lib: C.CDLL) -> None:
                                           vp], i32),
         "lsk_hip_cluster_periodic_hook": ([C.POINTER(TreeView), vp, vp, C.c_float, vp, i32, vp, vp, vp, vp], i32),
         "lsk_hip_cluster_periodic_border": ([C.POINTER(TreeView), vp, vp, C.c_float, vp, vp, vp, vp, vp, vp], i32),
+        "lsk_hip_radius_reach_count": ([C.POINTER(TreeView), vp, i64, vp, vp, i32, vp, vp, vp, vp, vp], i32),
+        "lsk_hip_radius_reach_fill": ([C.POINTER(TreeView), vp, vp, i64, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp],
+                                      i32),
         "lsk_hip_radius_profile_bins": ([], i32),
         "lsk_hip_radius_profile": ([C.POINTER(TreeView), vp, i64, vp, i32, vp, vp, vp, i64, i64, vp, vp], i32),
         "lsk_hip_pair_counts_ws_bytes": ([i64], C.c_size_t),

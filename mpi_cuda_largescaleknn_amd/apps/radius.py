@@ -3,6 +3,9 @@
     hipKNN_radius <points.float3> <queries.float3> (-r <radius> | --radii FILE | --point-radii FILE) [--squared]
                   -o <PREFIX> [--counts-only] [--unsorted] [--chunk N] [--max-pairs M]
                   [--period L | Lx,Ly,Lz] [--device auto|cuda|cpu] [--stats f.json] [-v]
+    hipKNN_radius <points.float3> <queries.float3> --reach QRADII.float PRADII.float [--rule either|both] [--squared]
+                  -o <PREFIX> [--counts-only] [--unsorted] [--chunk N] [--max-pairs M]
+                  [--period L | Lx,Ly,Lz] [--device auto|cuda|cpu] [--stats f.json] [-v]
     hipKNN_radius <points.float3> <queries.float3> --profile R1,R2,... [--squared] -o <PREFIX> [--pairs-only]
                   [--weights W.i64 [--query-weights WQ.i64]]
                   [--chunk N] [--period L | Lx,Ly,Lz] [--device auto|cuda|cpu] [--stats f.json] [-v]
@@ -19,7 +22,14 @@ row ascending by (distance, row) unless --unsorted. All files are headerless.
 
 --period L or Lx,Ly,Lz (inf: an open axis): the box is periodic, distances are those of the
 minimum image of the coordinate difference (lsknn_tools wrap brings coordinates into one
-period); a radius may not exceed half the period of a finite axis. Not with --point-radii.
+period); a radius may not exceed half the period of a finite axis. Not with --point-radii (--reach with an all-zero QRADII file is that
+search under a period).
+
+--reach QRADII.float PRADII.float: a radius on both sides, one float32 per query row and one per
+point row. --rule either (default): dist2 < max(query's, point's)², the symmetric
+neighbourhood; --rule both: dist2 < min(...)², the mutual one. Under "either" a query with
+radius 0 is still reached by points. The point radii are prepared once for all chunks. With
+--period every value of both files may not exceed half the period of a finite axis.
 
 --profile R1,R2,...: ascending radii (inf allowed); in place of the lists, the counts at every
 radius from one walk: PREFIX.profile (int32 [nq][B], row-major; column b = the counts of -r
@@ -85,8 +95,8 @@ def profile_arg(text: str) -> list[float]:
 
 
 def add_radius_options(ap: argparse.ArgumentParser) -> None:
-    """Exactly one of -r / --radii / --point-radii / --profile, --squared and --period (also
-    lsknn_tools rcheck)."""
+    """Exactly one of -r / --radii / --point-radii / --profile / --reach, --rule, --squared and
+    --period (also lsknn_tools rcheck)."""
     g = ap.add_mutually_exclusive_group(required=True)
     g.add_argument("-r", dest="radius", type=float, default=None, help="one radius for every query")
     g.add_argument("--radii", default=None, metavar="FILE",
@@ -95,6 +105,11 @@ def add_radius_options(ap: argparse.ArgumentParser) -> None:
                    help="headerless float32 file, one radius per point row: points whose own ball holds the query")
     g.add_argument("--profile", type=profile_arg, default=None, metavar="R1,R2,...",
                    help="ascending radii: the counts at every radius (PREFIX.profile) and their sums (PREFIX.pairs)")
+    g.add_argument("--reach", nargs=2, default=None, metavar=("QRADII", "PRADII"),
+                   help="two headerless float32 files, one radius per query row and one per point row: points "
+                        "with dist2 < max (--rule both: min) of the two squares")
+    ap.add_argument("--rule", choices=["either", "both"], default=None,
+                    help="with --reach: either ball reaches the other's centre (default), or both do")
     ap.add_argument("--pairs-only", action="store_true", help="with --profile: PREFIX.pairs (.wpairs) only")
     ap.add_argument("--weights", default=None, metavar="W.i64",
                     help="with --profile: headerless int64 file, one weight per point row: the sums of the weights "
@@ -119,6 +134,28 @@ def read_weights(path: str, what: str, rows: int, of: str) -> torch.Tensor:
     if w.shape[0] != rows:
         raise ValueError(f"{what} {path} holds {w.shape[0]} values, {of} has {rows} rows")
     return w
+
+
+def check_reach_options(ap: argparse.ArgumentParser, a: argparse.Namespace) -> None:
+    if a.rule is not None and a.reach is None:
+        ap.error("--rule needs --reach")
+    if a.reach is not None and a.rule is None:
+        a.rule = "either"
+
+
+def read_reach(a: argparse.Namespace, nq: int, n: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """The two radius files of --reach (host tensors), every value checked: >= 0, not NaN and,
+    under --period, within its bound. ValueError otherwise."""
+    qrad = read_radii(a.reach[0], "--reach", nq, a.queries)
+    prad = read_radii(a.reach[1], "--reach", n, a.points)
+    upper = math.inf if a.period is None else E.period_radius_bound(a.period, a.squared)
+    for path, r in zip(a.reach, (qrad, prad)):
+        if not bool((r >= 0).all()):
+            raise ValueError(f"--reach {path}: every value must be >= 0 and not NaN")
+        if not bool((r <= upper).all()):
+            raise ValueError(f"--reach {path}: a value exceeds half the period of a finite axis "
+                             f"({'squared ' if a.squared else ''}bound {upper})")
+    return qrad, prad
 
 
 def check_weight_options(ap: argparse.ArgumentParser, a: argparse.Namespace) -> None:
@@ -152,6 +189,7 @@ def parse(argv: list[str]) -> argparse.Namespace:
     if a.pairs_only and a.profile is None:
         ap.error("--pairs-only needs --profile")
     check_weight_options(ap, a)
+    check_reach_options(ap, a)
     if a.profile is not None and (a.counts_only or a.unsorted):
         ap.error("--profile writes no lists: not with --counts-only / --unsorted")
     return a
@@ -286,7 +324,7 @@ def main(argv: list[str] | None = None) -> int:
                 json.dump(rec, f, indent=1)
         return 0
     # the search of queries [b, e) of the file: one radius, one per query (sliced with the
-    # queries), or one per point (prepared once)
+    # queries), one per point (prepared once), or both
     try:
         if a.radii is not None:
             qrad = read_radii(a.radii, "--radii", nq, a.queries)
@@ -299,6 +337,17 @@ def main(argv: list[str] | None = None) -> int:
             def lists_fn(q, b, e):
                 return E.radius_neighbors(index, q, qrad[b:e].to(dev), sort=not a.unsorted, max_pairs=a.max_pairs,
                                           squared=a.squared, **per)
+        elif a.reach is not None:
+            qrad, prow = read_reach(a, nq, index.n)
+            prad = E.prepare_point_radii(index, prow.to(dev), squared=a.squared)
+
+            def count_fn(q, b, e):
+                return E.reach_counts(index, q, qrad[b:e].to(dev), prad, rule=a.rule, squared=a.squared, stats=stats,
+                                      **per)
+
+            def lists_fn(q, b, e):
+                return E.reach_neighbors(index, q, qrad[b:e].to(dev), prad, rule=a.rule, squared=a.squared,
+                                         sort=not a.unsorted, max_pairs=a.max_pairs, **per)
         elif a.point_radii is not None:
             prad = E.prepare_point_radii(index, read_radii(a.point_radii, "--point-radii", index.n, a.points).to(dev),
                                          squared=a.squared)
@@ -364,6 +413,8 @@ def main(argv: list[str] | None = None) -> int:
                "kernels": E.kernels_used(), "radius_search": stats.counters}
         if a.radius is None:
             rec.update({"radii": a.radii, "point_radii": a.point_radii})
+            if a.reach is not None:
+                rec.update({"reach": list(a.reach), "rule": a.rule})
         if a.squared:
             rec["squared"] = True
         if a.period is not None:

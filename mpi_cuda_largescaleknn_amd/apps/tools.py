@@ -10,8 +10,8 @@
            -> exact CPU oracle on sampled points, bitwise compare (replaces the reference's
               disabled '#if 0' RES dump, unorderedDataVariant.cu:215-227)
     python -m mpi_cuda_largescaleknn_amd.apps.tools rcheck in.float3 q.float3 PREFIX [--samples S]
-           (-r R | --radii FILE | --point-radii FILE) [--squared] [--counts-only] [--unsorted]
-           [--period L | Lx,Ly,Lz]
+           (-r R | --radii FILE | --point-radii FILE | --reach QRADII PRADII [--rule either|both])
+           [--squared] [--counts-only] [--unsorted] [--period L | Lx,Ly,Lz]
            -> hipKNN_radius' PREFIX.count (and .offsets / .ids / .dist) for q.float3 against the
               brute-force oracle: every count's consistency with the offsets, sampled rows bitwise
     python -m mpi_cuda_largescaleknn_amd.apps.tools rcheck in.float3 q.float3 PREFIX --profile R1,R2,... [--squared]
@@ -314,6 +314,9 @@ def rcheck(a) -> int:
         return _rcheck_weighted(a, pts, qry)
     if a.profile is not None:
         return _rcheck_profile(a, pts, qry)
+    if a.rule is not None and a.reach is None:
+        print("rcheck: --rule needs --reach")
+        return 1
     if a.samples is None:
         a.samples = 1000
     if a.period is not None and a.point_radii is not None:
@@ -328,6 +331,20 @@ def rcheck(a) -> int:
                 return (K.radius_periodic_count_cpu(pts, qry[idx], cut2, a.period),
                         lambda: K.radius_periodic_cpu(pts, qry[idx], cut2, a.period))
             return K.radius_count_cpu(pts, qry[idx], cut2), lambda: K.radius_cpu(pts, qry[idx], cut2)
+    elif a.reach is not None:
+        from .radius import read_radii
+        try:
+            qrad = read_radii(a.reach[0], "--reach", nq, a.queries)
+            prad = read_radii(a.reach[1], "--reach", pts.shape[0], a.inp)
+        except ValueError as e:
+            print(e)
+            return 1
+        qc2, pc2 = (qrad, prad) if a.squared else (qrad * qrad, prad * prad)
+        rule = a.rule or "either"
+
+        def oracle(idx):
+            return (K.radius_reach_count_cpu(pts, qry[idx], qc2[idx], pc2, rule, a.period),
+                    lambda: K.radius_reach_cpu(pts, qry[idx], qc2[idx], pc2, rule, a.period))
     else:
         from .radius import read_radii
         try:

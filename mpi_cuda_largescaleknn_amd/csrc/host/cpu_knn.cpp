@@ -478,6 +478,56 @@ extern "C" void lsk_cpu_radius_periodic_fill(const float *pts, int64_t n, const 
   });
 }
 
+// Two-sided radii: point i is in row q iff d² < max(qcut2[q], pcut2[i]) (rule 0, either) or d² <
+// min(qcut2[q], pcut2[i]) (rule 1, both); d² = dist2, or pdist2 under a period (optional).
+namespace {
+
+inline float reach_cut(float cq, float cp, int rule) { return rule ? std::min(cq, cp) : std::max(cq, cp); }
+
+inline float reach_d2(const vec3f &q, const vec3f &p, const float *period) {
+  return period ? pdist2(q, p, period) : lsk::dist2(q, p);
+}
+
+}  // namespace
+
+extern "C" void lsk_cpu_radius_reach_count(const float *pts, int64_t n, const float *qry, int64_t nq,
+                                           const float *qcut2, const float *pcut2, int rule, const float *period,
+                                           int32_t *counts, int nthreads) {
+  const vec3f *P = (const vec3f *)pts;
+  const vec3f *Q = (const vec3f *)qry;
+  parallel_for(nq, nthreads, [&](int64_t b, int64_t e) {
+    for (int64_t qi = b; qi < e; qi++) {
+      int32_t c = 0;
+      for (int64_t i = 0; i < n; i++) c += reach_d2(Q[qi], P[i], period) < reach_cut(qcut2[qi], pcut2[i], rule);
+      counts[qi] = c;
+    }
+  });
+}
+
+extern "C" void lsk_cpu_radius_reach_fill(const float *pts, int64_t n, const float *qry, int64_t nq,
+                                          const float *qcut2, const float *pcut2, int rule, const float *period,
+                                          const int64_t *offsets, int32_t *out_idx, float *out_d2, int nthreads) {
+  const vec3f *P = (const vec3f *)pts;
+  const vec3f *Q = (const vec3f *)qry;
+  parallel_for(nq, nthreads, [&](int64_t b, int64_t e) {
+    std::vector<uint64_t> d;  // d2 bits << 32 | input row, as lsk_cpu_knn_brute
+    for (int64_t qi = b; qi < e; qi++) {
+      d.clear();
+      for (int64_t i = 0; i < n; i++) {
+        const float v = reach_d2(Q[qi], P[i], period);
+        if (v < reach_cut(qcut2[qi], pcut2[i], rule)) d.push_back(((uint64_t)lsk::fbits(v) << 32) | (uint32_t)i);
+      }
+      std::sort(d.begin(), d.end());
+      // (offsets come from lsk_cpu_radius_reach_count with the same cutoffs)
+      const size_t m = std::min<size_t>(d.size(), (size_t)(offsets[qi + 1] - offsets[qi]));
+      for (size_t j = 0; j < m; j++) {
+        out_idx[offsets[qi] + (int64_t)j] = (int32_t)(uint32_t)d[j];
+        out_d2[offsets[qi] + (int64_t)j] = lsk::bitsf((uint32_t)(d[j] >> 32));
+      }
+    }
+  });
+}
+
 // Radius profile: out[q * nb + b] = #{ i : dist2(q, p_i) < cut2s[b] } for the ascending cutoffs
 // cut2s[0 .. nb), from one pass over the points per query; period (optional): pdist2 instead.
 // A pair goes to shell b0 = #{ b : !(d² < cut2s[b]) } (the cutoffs ascend, so that is the first b

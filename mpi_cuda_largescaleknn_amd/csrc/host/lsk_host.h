@@ -130,6 +130,15 @@ void lsk_cpu_radius_periodic_fill(const float *pts, int64_t n, const float *qry,
                                   int32_t *out_idx, float *out_d2, int nthreads);
 void lsk_cpu_cluster_periodic(const float *pts, int64_t n, float cut2, int min_pts, const float *period,
                               int32_t *labels, uint8_t *core, int nthreads);
+// The radius search with a squared cutoff on both sides (qcut2 [nq], pcut2 [n], both given):
+// point i is in row q iff d² < max(qcut2[q], pcut2[i]) (rule = 0, either) or d² < min(qcut2[q],
+// pcut2[i]) (rule = 1, both), strictly; d² = dist2, or with period (optional, as above) the
+// minimum image. Same CSR form and row order.
+void lsk_cpu_radius_reach_count(const float *pts, int64_t n, const float *qry, int64_t nq, const float *qcut2,
+                                const float *pcut2, int rule, const float *period, int32_t *counts, int nthreads);
+void lsk_cpu_radius_reach_fill(const float *pts, int64_t n, const float *qry, int64_t nq, const float *qcut2,
+                               const float *pcut2, int rule, const float *period, const int64_t *offsets,
+                               int32_t *out_idx, float *out_d2, int nthreads);
 // Radius profile by brute force, one pass over the points per query: out[q * nb + b] (int32 [nq,
 // nb]) = #{ i : dist2(q, p_i) < cut2s[b] } for nb >= 1 ascending cutoffs (each >= 0, +inf
 // allowed, no NaN), i.e. column b is lsk_cpu_radius_count at cut2s[b]; period (optional, as

@@ -1239,7 +1239,12 @@ def prepare_point_radii(index: LocalIndex, point_radii: torch.Tensor, squared: b
     the largest cutoff below every node. The index itself is not written. Every point_radius_*
     function that takes an index accepts the result in place of the tensor, so a caller that
     sends queries in chunks prepares the radii once."""
-    cut2 = _cut2_tensor("prepare_point_radii", "point_radii", point_radii, index.n, index.device, squared)
+    return _prepared_radii(index, _cut2_tensor("prepare_point_radii", "point_radii", point_radii, index.n,
+                                               index.device, squared))
+
+
+def _prepared_radii(index: LocalIndex, cut2: torch.Tensor) -> PointRadii:
+    """The PointRadii of checked squared cutoffs (rows of the indexed array)."""
     if not K.is_gpu(index.pts) or index.n == 0:
         return PointRadii(index, cut2, None, None)
     cut2_sorted = cut2[index.perm[:index.n].long()].contiguous()
@@ -2238,7 +2243,9 @@ def point_radius_counts(index: LocalIndex, queries: torch.Tensor, point_radii, s
     query; a negative or NaN entry raises ValueError before any kernel runs. The walk culls a
     node with the largest cutoff below it; there is no whole-box shortcut (it would need the
     smallest cutoff below a node), so radius_box_accepts stays 0 in `stats`. The scatter
-    searches have no periodic form: a `period` raises ValueError ("not supported")."""
+    searches have no periodic form: a `period` raises ValueError ("not supported"); under a
+    period reach_counts / reach_neighbors with query_radii=0.0 and rule="either" are this
+    search."""
     _no_period("point_radius_counts", period)
     queries = _check_foreign("point_radius_counts", index, queries)
     prad = _point_radii("point_radius_counts", index, point_radii, squared)
@@ -2248,7 +2255,8 @@ def point_radius_counts(index: LocalIndex, queries: torch.Tensor, point_radii, s
 def point_radius_neighbors(index: LocalIndex, queries: torch.Tensor, point_radii, squared: bool = False,
                            sort: bool = True, max_pairs: int = 1 << 28, period=None) -> tuple:
     """The CSR lists of radius_neighbors under the per-point predicate of point_radius_counts:
-    row q holds every point p of `index` with dist2(q, p) < cut2[p], in the same order."""
+    row q holds every point p of `index` with dist2(q, p) < cut2[p], in the same order. No
+    periodic form (see point_radius_counts): reach_neighbors with query_radii=0.0 has one."""
     _no_period("point_radius_neighbors", period)
     queries = _check_foreign("point_radius_neighbors", index, queries)
     prad = _point_radii("point_radius_neighbors", index, point_radii, squared)
@@ -2285,6 +2293,157 @@ def point_radius_self_neighbors(points: torch.Tensor, point_radii: torch.Tensor,
     points that have i among their k nearest, ties at the k-th distance left out)."""
     _no_period("point_radius_self_neighbors", period)
     return point_radius_query_neighbors(points, points, point_radii, squared=squared, sort=sort, max_pairs=max_pairs)
+
+
+# ---- two-sided radii: a cutoff on the query and on the point at once (radius_reach.hip)
+def _reach_cutoffs(what: str, index: LocalIndex, queries: torch.Tensor, query_radii, point_radii, rule: str,
+                   squared: bool, period) -> tuple:
+    """The checked arguments of a two-sided search: (queries, qcut2 float32 [nq], PointRadii, period
+    values or None). Every ValueError of reach_counts is raised here, before any kernel runs."""
+    K.reach_rule(what, rule)
+    per = None if period is None else K.check_period(what, period)
+    if index.qrot is not None or index.line:
+        raise ValueError(f"{what}: an index built in a rotated frame or sorted by line keys is not supported")
+    queries = _check_foreign(what, index, queries)
+    nq, dev = queries.shape[0], index.device
+    upper = None
+    if per is not None and not math.isinf(period_radius_bound(per, squared)):
+        upper = period_radius_bound(per, squared)
+    if isinstance(query_radii, torch.Tensor):
+        qcut2 = _cut2_tensor(what, "query_radii", query_radii, nq, dev, squared, upper=upper)
+    elif isinstance(query_radii, (int, float)) and not isinstance(query_radii, bool):
+        cut2 = _radius_cut2(what, query_radii, squared)
+        if per is not None:
+            check_period_radius(what, query_radii, squared, per, name="query_radii")
+        qcut2 = torch.full((nq,), cut2, dtype=torch.float32, device=dev)
+    else:
+        raise ValueError(f"{what}: query_radii must be a float32 [{nq}] tensor or one number "
+                         f"(got {type(query_radii).__name__})")
+    if isinstance(point_radii, PointRadii):
+        prad = _point_radii(what, index, point_radii, squared)
+        if upper is not None and index.n:
+            upper2 = period_radius_bound(per, True)
+            if not bool((prad.cut2 <= upper2).all()):
+                raise ValueError(f"{what}: every entry of point_radii must be at most half the period of every "
+                                 f"finite axis (squared bound {upper2} here)")
+    else:
+        prad = _prepared_radii(index, _cut2_tensor(what, "point_radii", point_radii, index.n, dev, squared,
+                                                   upper=upper))
+    return queries, qcut2, prad, per
+
+
+def _reach_counts(index: LocalIndex, queries: torch.Tensor, qcut2: torch.Tensor, prad: PointRadii, rule: str,
+                  per: tuple | None, stats: KnnStats | None, _sorted: tuple | None = None) -> torch.Tensor:
+    nq, n = queries.shape[0], index.n
+    if nq == 0 or n == 0:
+        return torch.zeros(nq, dtype=torch.int32, device=index.device)
+    if not K.is_gpu(index.pts):
+        KERNELS_USED.add("cpu")
+        return K.radius_reach_count_cpu(_input_order(index), queries, qcut2, prad.cut2, rule, per)
+    qsorted, qperm = _sorted if _sorted is not None else prepare_queries(index, queries, locate=False)[:2]
+    names = _RADIUS_STATS if per is None else _RADIUS_PERIODIC_STATS
+    raw = torch.zeros(len(names), dtype=torch.int64, device=index.device) if stats is not None else None
+    tree = (index.pts, prad.nodes, index.qnodes, n, index.depth)
+    counts = K.radius_reach_count_gpu(tree, qsorted, nq, qperm, qcut2, prad.cut2_sorted, rule, period=per, stats=raw)
+    KERNELS_USED.add("radius_reach")
+    _add_stats(stats, names, raw)
+    return counts
+
+
+def reach_counts(index: LocalIndex, queries: torch.Tensor, query_radii, point_radii, rule: str = "either",
+                 squared: bool = False, stats: KnnStats | None = None, period=None) -> torch.Tensor:
+    """int32 [nq], in query order: the two-sided radius search, a radius on the query and on the
+    point at once. With cq[q] and cp[p] the squared cutoffs, p counts for q iff
+        rule="either":  d2 < max(cq[q], cp[p])   (one ball reaches the other's centre)
+        rule="both":    d2 < min(cq[q], cp[p])   (each ball reaches the other's centre)
+    strictly, d2 the dist2 of radius_counts, under `period` its minimum image. max and min are
+    taken on float32 values, so the predicate is symmetric in its bits: with smoothing lengths on
+    both sides "either" is the SPH neighbour list, and with squared k-th distances as radii the
+    two rules give the symmetric and the mutual k-NN graph.
+
+    query_radii: float32 [nq] on the index's device, or one number for every query. point_radii:
+    float32 [n] in the order of the indexed array's rows, or the result of prepare_point_radii
+    for this index (a caller that sends queries in chunks prepares once). squared=True: both
+    hold squared cutoffs. A NaN or infinite query counts nothing. Under "either" a query with
+    radius 0 is still reached by points (query_radii=0.0 is point_radius_counts, and the only
+    form of it under a period); under "both" a query or a point with radius 0 selects nothing.
+    inf is allowed in the open box. period: as in radius_counts; every entry of both sides may
+    then not exceed half the period of a finite axis. None: the open box, a walk without an
+    image loop; (inf, inf, inf) gives the same result bit for bit.
+
+    One walk serves both sides: a node is culled with max (min) of the widest live query cutoff
+    and the largest point cutoff below it. Under "either" a lane counts a node whole when its own
+    ball covers it (radius_box_accepts); "both" has no such shortcut. `stats` receives the
+    radius_* counters and, under a period, radius_images.
+
+    ValueError before any kernel runs: a rule other than the two; radii of a wrong type, shape
+    or device; a negative or NaN entry; radii prepared for another index; under a period an
+    entry above the bound, or a bad period; an index in a rotated frame or sorted by line keys."""
+    queries, qcut2, prad, per = _reach_cutoffs("reach_counts", index, queries, query_radii, point_radii, rule,
+                                               squared, period)
+    return _reach_counts(index, queries, qcut2, prad, rule, per, stats)
+
+
+def reach_neighbors(index: LocalIndex, queries: torch.Tensor, query_radii, point_radii, rule: str = "either",
+                    squared: bool = False, sort: bool = True, max_pairs: int = 1 << 28, period=None) -> tuple:
+    """The CSR lists of radius_neighbors under the predicate of reach_counts: row q holds every
+    point p of `index` selected for q, ascending by (dist2 bits, row of the indexed array)
+    (sort=False: unspecified order); dist holds the final (under a period: periodic) distances.
+    More than `max_pairs` pairs raise ValueError before the lists are allocated."""
+    what = "reach_neighbors"
+    queries, qcut2, prad, per = _reach_cutoffs(what, index, queries, query_radii, point_radii, rule, squared, period)
+    nq, n = queries.shape[0], index.n
+    dev = index.device
+    gpu = K.is_gpu(index.pts)
+    if nq == 0 or n == 0:
+        return _empty_csr(nq, dev)
+    prep = prepare_queries(index, queries, locate=False)[:2] if gpu else None
+    counts = _reach_counts(index, queries, qcut2, prad, rule, per, None, _sorted=prep)
+    offsets = torch.zeros(nq + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, dtype=torch.int64, out=offsets[1:])
+    total, longest = (int(v) for v in torch.stack((offsets[nq], counts.max().long())).tolist())  # the only sync
+    if total > max_pairs:
+        raise ValueError(f"{what}: {total} pairs within the radii exceed max_pairs = {max_pairs}; "
+                         "query fewer points at a time or raise max_pairs")
+    if not gpu:
+        o2, idx, d2 = K.radius_reach_cpu(_input_order(index), queries, qcut2, prad.cut2, rule, per)
+        return o2, idx, K.finalize_distances(d2)
+    qsorted, qperm = prep
+    tree = (index.pts, prad.nodes, index.qnodes, n, index.depth)
+    idx, dist, err = K.radius_reach_fill_gpu(tree, index.perm, qsorted, nq, qperm, offsets, total, longest, qcut2,
+                                             prad.cut2_sorted, rule, period=per, sort=sort)
+    LAST_RADIUS_ERRORS[0] = int(err.item()) & 0xFFFFFFFF
+    if LAST_RADIUS_ERRORS[0]:
+        raise NativeError(f"{what}: {LAST_RADIUS_ERRORS[0]} rows were not filled to their count "
+                          "(the count pass and the fill pass disagree: a bug)")
+    return offsets, idx, dist
+
+
+def reach_query_counts(points: torch.Tensor, queries: torch.Tensor, query_radii, point_radii: torch.Tensor,
+                       rule: str = "either", squared: bool = False, stats: KnnStats | None = None,
+                       period=None) -> torch.Tensor:
+    """reach_counts over an index built once from `points`, in the points' own frame."""
+    index = _point_query_index("reach_query_counts", points, queries)
+    return reach_counts(index, queries, query_radii, point_radii, rule=rule, squared=squared, stats=stats,
+                        period=period)
+
+
+def reach_query_neighbors(points: torch.Tensor, queries: torch.Tensor, query_radii, point_radii: torch.Tensor,
+                          rule: str = "either", squared: bool = False, sort: bool = True,
+                          max_pairs: int = 1 << 28, period=None) -> tuple:
+    """reach_neighbors over an index built once from `points`, in the points' own frame."""
+    index = _point_query_index("reach_query_neighbors", points, queries)
+    return reach_neighbors(index, queries, query_radii, point_radii, rule=rule, squared=squared, sort=sort,
+                           max_pairs=max_pairs, period=period)
+
+
+def reach_self_neighbors(points: torch.Tensor, radii: torch.Tensor, rule: str = "either", squared: bool = False,
+                         sort: bool = True, max_pairs: int = 1 << 28, period=None) -> tuple:
+    """reach_query_neighbors with the points as their own queries and `radii` (float32 [n]) on
+    both sides: the SPH neighbour list, d2 < max(h_i, h_j)^2 ("both": min). The relation is
+    symmetric: i is in row j iff j is in row i, with the same distance bits."""
+    return reach_query_neighbors(points, points, radii, radii, rule=rule, squared=squared, sort=sort,
+                                 max_pairs=max_pairs, period=period)
 
 
 # ------------------------------------------------------------------ density clustering

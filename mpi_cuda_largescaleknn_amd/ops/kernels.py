@@ -1130,6 +1130,118 @@ def radius_periodic_fill_gpu(tree: tuple, perm: torch.Tensor, qsorted: torch.Ten
     return idx, dist, err
 
 
+# ---- two-sided radii: a cutoff per query and per point (radius_reach.hip)
+REACH_RULES = {"either": 0, "both": 1}  # LSK_REACH_EITHER / LSK_REACH_BOTH
+
+
+def reach_rule(what: str, rule) -> int:
+    """The native code of rule "either" (d2 < max(cq, cp)) or "both" (d2 < min(cq, cp));
+    anything else raises ValueError."""
+    if not isinstance(rule, str) or rule not in REACH_RULES:
+        raise ValueError(f"{what}: rule must be 'either' or 'both' (got {rule!r})")
+    return REACH_RULES[rule]
+
+
+def _reach_cpu_args(what: str, points, queries, qcut2, pcut2, rule, period):
+    code = reach_rule(what, rule)
+    per = None if period is None else check_period(what, period)
+    pts = points.contiguous().float().cpu()
+    q = queries.contiguous().float().cpu()
+    qc = _var_cut2_cpu(what, qcut2, q.shape[0])
+    pc = _var_cut2_cpu(what, pcut2, pts.shape[0])
+    if qc is None or pc is None:
+        raise ValueError(f"{what}: both qcut2 and pcut2 are required")
+    return pts, q, qc, pc, code, None if per is None else _period_c(per)
+
+
+def radius_reach_count_cpu(points: torch.Tensor, queries: torch.Tensor, qcut2: torch.Tensor, pcut2: torch.Tensor,
+                           rule: str = "either", period=None) -> torch.Tensor:
+    """CPU oracle (brute force) of the two-sided radius counts: int32 [nq], per query q the number
+    of rows p of `points` with d2 < max(qcut2[q], pcut2[p]) (rule "either") or d2 < min(qcut2[q],
+    pcut2[p]) ("both"), strict; qcut2 float32 [nq], pcut2 float32 [n] in the order of `points`.
+    d2 is dist2, or under `period` the minimum image of radius_periodic_count_cpu."""
+    pts, q, qc, pc, code, per = _reach_cpu_args("radius_reach_count_cpu", points, queries, qcut2, pcut2, rule, period)
+    counts = torch.empty(q.shape[0], dtype=torch.int32)
+    _native.host().lsk_cpu_radius_reach_count(_ptr(pts), pts.shape[0], _ptr(q), q.shape[0], _ptr(qc), _ptr(pc), code,
+                                              per, _ptr(counts), _nthreads())
+    return counts
+
+
+def radius_reach_cpu(points: torch.Tensor, queries: torch.Tensor, qcut2: torch.Tensor, pcut2: torch.Tensor,
+                     rule: str = "either", period=None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """CPU oracle of the two-sided radius lists (brute force), the CSR form and row order of
+    radius_cpu under the predicate of radius_reach_count_cpu."""
+    pts, q, qc, pc, code, per = _reach_cpu_args("radius_reach_cpu", points, queries, qcut2, pcut2, rule, period)
+    nq = q.shape[0]
+    counts = torch.empty(nq, dtype=torch.int32)
+    lib = _native.host()
+    lib.lsk_cpu_radius_reach_count(_ptr(pts), pts.shape[0], _ptr(q), nq, _ptr(qc), _ptr(pc), code, per,
+                                   _ptr(counts), _nthreads())
+    offsets = torch.zeros(nq + 1, dtype=torch.int64)
+    torch.cumsum(counts, 0, dtype=torch.int64, out=offsets[1:])
+    total = int(offsets[nq])
+    idx = torch.empty(total, dtype=torch.int32)
+    d2 = torch.empty(total, dtype=torch.float32)
+    lib.lsk_cpu_radius_reach_fill(_ptr(pts), pts.shape[0], _ptr(q), nq, _ptr(qc), _ptr(pc), code, per,
+                                  _ptr(offsets), _ptr(idx), _ptr(d2), _nthreads())
+    return offsets, idx, d2
+
+
+def _reach_view(what: str, tree: tuple, qsorted: torch.Tensor, nq: int, out_perm: torch.Tensor,
+                qcut2: torch.Tensor, pcut2: torch.Tensor):
+    dev = tree[0].device
+    for t, cnt, nm in ((qcut2, nq, "qcut2"), (pcut2, tree[3], "pcut2")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.shape != (cnt,) \
+                or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{what}: {nm} float32 [{cnt}], contiguous, on the tree's device")
+    return _walk_view(what, tree, qsorted, nq, out_perm)
+
+
+def radius_reach_count_gpu(tree: tuple, qsorted: torch.Tensor, nq: int, out_perm: torch.Tensor, qcut2: torch.Tensor,
+                           pcut2: torch.Tensor, rule: str, period: tuple[float, float, float] | None = None,
+                           stats: torch.Tensor | None = None) -> torch.Tensor:
+    """The count pass of the two-sided radius search (radius_reach.hip), as radius_count_gpu.
+    qcut2: float32 [nq] squared cutoffs in query order; pcut2: float32 [n] in the order of the
+    tree's sorted points, the tree's node array being a copy annotated with them
+    (tree_set_radii). Entries >= 0, no NaN, within the period's bound: the caller checks. period:
+    check_period's values, or None for the open box (the walk without an image loop). stats:
+    optional zeroed int64 [4] (period: [RADIUS_PERIODIC_STATS])."""
+    code = reach_rule("radius_reach_count_gpu", rule)
+    tv = _reach_view("radius_reach_count_gpu", tree, qsorted, nq, out_perm, qcut2, pcut2)
+    counts = torch.empty(nq, dtype=torch.int32, device=tree[0].device)
+    check(_native.hip().lsk_hip_radius_reach_count(C.byref(tv), _ptr(qsorted), int(nq), _ptr(qcut2), _ptr(pcut2),
+                                                   code, None if period is None else _period_c(period),
+                                                   _ptr(out_perm), _ptr(counts), _ptr(stats), _stream(tree[0])),
+          "radius_reach_count")
+    return counts
+
+
+def radius_reach_fill_gpu(tree: tuple, perm: torch.Tensor, qsorted: torch.Tensor, nq: int, out_perm: torch.Tensor,
+                          offsets: torch.Tensor, total: int, longest: int, qcut2: torch.Tensor, pcut2: torch.Tensor,
+                          rule: str, period: tuple[float, float, float] | None = None,
+                          sort: bool = True) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The fill and sort passes of the two-sided radius search, as radius_fill_gpu (the sort is
+    lsk_hip_radius_sort itself); cutoffs, rule and period as for radius_reach_count_gpu."""
+    code = reach_rule("radius_reach_fill_gpu", rule)
+    tv = _reach_view("radius_reach_fill_gpu", tree, qsorted, nq, out_perm, qcut2, pcut2)
+    dev = tree[0].device
+    if offsets.dtype != torch.int64 or offsets.numel() != nq + 1 or not offsets.is_contiguous() or offsets.device != dev \
+            or perm.dtype != torch.int32 or perm.numel() < tree[3] or not perm.is_contiguous() or perm.device != dev:
+        raise ValueError("radius_reach_fill_gpu: offsets int64 [nq + 1] and perm int32 [n], contiguous, "
+                         "on the tree's device")
+    lib = _native.hip()
+    idx = torch.empty(total, dtype=torch.int32, device=dev)
+    dist = torch.empty(total, dtype=torch.float32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    check(lib.lsk_hip_radius_reach_fill(C.byref(tv), _ptr(perm), _ptr(qsorted), int(nq), _ptr(qcut2), _ptr(pcut2),
+                                        code, None if period is None else _period_c(period), _ptr(out_perm),
+                                        _ptr(offsets), _ptr(idx), _ptr(dist), _ptr(err), _stream(tree[0])),
+          "radius_reach_fill")
+    check(lib.lsk_hip_radius_sort(_ptr(offsets), int(nq), int(total), int(longest), _ptr(idx), _ptr(dist),
+                                  1 if sort else 0, _stream(tree[0])), "radius_sort")
+    return idx, dist, err
+
+
 def cluster_periodic_gpu(tree: tuple, perm: torch.Tensor, core_sorted: torch.Tensor, cut2: float,
                          period: tuple[float, float, float], fof: bool, border: bool, half: bool = False,
                          stats: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:

@@ -9,6 +9,8 @@
     python scripts/radius_bench.py --pairs-2d BPxBL [--smu] [-r R] [--self-queries] [--points ..] [--queries ..]
                                    [--steps ..] [--warmup ..] [--period ..] [--skip-pair-list] [--weights]
                                    [--los midpoint [--observer ox,oy,oz]]
+    python scripts/radius_bench.py --reach either|both [--period ..] [--dist uniform|clustered] [--kth K]
+                                   [--points ..] [--steps ..] [--warmup ..]
 
 Uniform points in the unit cube and uniform queries from another seed; the radius is the one
 whose ball holds --mean points at the data's density (queries near the faces see fewer, so
@@ -30,6 +32,16 @@ step so that drift on a shared host hits them alike:
 the extent; not with point-kth); the JSON then carries radius_images / groups, the image
 walks per query group of the count pass, beside the times.
 Prints one JSON line. Sampled rows are checked against brute force.
+
+--reach either|both: the two-sided search with the points as their own queries and every
+point's k-th neighbour distance (k = --kth) as its radius on both sides, prepared once outside
+the timed region (--dist clustered: 100 Gaussian blobs, sigma 0.01, wrapped into the unit cube).
+Timed alternately as above: reach_neighbors (sorted) and reach_counts; and, without --period,
+the two walks the search replaces, radius_neighbors with the radius tensor (gather) and
+point_radius_neighbors (scatter), whose sum `two_walks_s` holds no union of the two results: the
+row-wise union a caller had to write comes on top of it. With --period no earlier path exists:
+the open run of the same inputs is timed beside the periodic one. The JSON carries the medians
+and the radius_* counters of every count walk; sampled rows are checked against brute force.
 
 --profile B: the radius profile instead. B log-spaced radii from r / 8 up to r (-r, default the
 radius of --mean), on one index and one set of queries (--self-queries: the points themselves),
@@ -138,6 +150,85 @@ def profile_bench(a, p: torch.Tensor, q: torch.Tensor, r: float, per: dict) -> i
         rec["period"] = list(a.period)
     print(json.dumps(rec), flush=True)
     return 0 if same_columns and same_sums else 1
+
+
+def reach_bench(a, p: torch.Tensor, per: dict) -> int:
+    """--reach either|both: reach_neighbors / reach_counts beside the gather and the scatter walk
+    (open box) or beside their own open run (--period)."""
+    rule, n = a.reach, p.shape[0]
+    index = E.build_index(p)
+    h = E.knn_distances(p, a.kth)
+    prad = E.prepare_point_radii(index, h)
+    big = {"max_pairs": (1 << 31) - 1}  # (k-th distance radii on 1e7 points select more than 2^28 pairs)
+    out = {}
+    cases = {
+        "reach": lambda: out.__setitem__("reach", E.reach_neighbors(index, p, h, prad, rule=rule, **big, **per)),
+        "reach_counts": lambda **kw: out.__setitem__("counts", E.reach_counts(index, p, h, prad, rule=rule, **per, **kw)),
+    }
+    if a.period is None:
+        cases["gather"] = lambda: out.__setitem__("gather", E.radius_neighbors(index, p, h, **big))
+        cases["scatter"] = lambda: out.__setitem__("scatter", E.point_radius_neighbors(index, p, prad, **big))
+        cases["gather_counts"] = lambda **kw: out.__setitem__("gc", E.radius_counts(index, p, h, **kw))
+        cases["scatter_counts"] = lambda **kw: out.__setitem__("sc", E.point_radius_counts(index, p, prad, **kw))
+    else:
+        cases["reach_open"] = lambda: out.__setitem__("open", E.reach_neighbors(index, p, h, prad, rule=rule, **big))
+        cases["reach_open_counts"] = lambda **kw: out.__setitem__(
+            "oc", E.reach_counts(index, p, h, prad, rule=rule, **kw))
+    times = {name: [] for name in cases}
+    for step in range(a.warmup + a.steps):
+        for name, fn in cases.items():
+            out.clear()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            if step >= a.warmup:
+                times[name].append(time.perf_counter() - t0)
+    med = {name: statistics.median(ts) for name, ts in times.items()}
+    counters = {}
+    for name, fn in cases.items():
+        if name.endswith("counts"):
+            st = E.KnnStats()
+            fn(stats=st)
+            counters[name] = dict(st.counters)
+    offsets, idx, dist = E.reach_neighbors(index, p, h, prad, rule=rule, **big, **per)
+    counts = E.reach_counts(index, p, h, prad, rule=rule, **per)
+    smp = torch.randint(0, n, (64,), generator=torch.Generator().manual_seed(3))
+    c2 = (h * h).cpu()
+    ro, ri, rd2 = K.radius_reach_cpu(p.cpu(), p[smp.to(p.device)].cpu(), c2[smp], c2, rule, a.period)
+    rd = K.finalize_distances(rd2)
+    off = offsets.cpu()
+    exact = 0
+    for j, qi in enumerate(smp.tolist()):
+        gi, gd = idx[off[qi]:off[qi + 1]].cpu(), dist[off[qi]:off[qi + 1]].cpu()
+        exact += int(torch.equal(gi, ri[ro[j]:ro[j + 1]]) and torch.equal(gd, rd[ro[j]:ro[j + 1]]))
+    consistent = bool(torch.equal(torch.cumsum(counts, 0, dtype=torch.int64), offsets[1:]))
+    rec = {
+        "points": n, "queries": n, "self_queries": True, "dist": a.dist, "reach": rule, "kth": a.kth,
+        "pairs": int(offsets[-1]), "mean_count": int(offsets[-1]) / n, "max_count": int(counts.max()),
+        "steps": a.steps, "warmup": a.warmup, **{f"{name}_s": t for name, t in med.items()},
+        "spread": {name: [min(ts), max(ts)] for name, ts in times.items()}, "counters": counters,
+        "sampled_exact": f"{exact}/64", "offsets_are_count_sums": consistent,
+    }
+    if a.period is None:
+        rec["two_walks_s"] = med["gather"] + med["scatter"]
+        rec["reach_over_two_walks"] = med["reach"] / rec["two_walks_s"]
+        rec["union_included"] = False
+    else:
+        groups = (n + 63) // 64
+        rec.update({"period": list(a.period), "periodic_over_open": med["reach"] / med["reach_open"],
+                    "images_per_group": counters["reach_counts"]["radius_images"] / groups})
+    print(json.dumps(rec), flush=True)
+    return 0 if exact == 64 and consistent else 1
+
+
+def clustered_points(n: int, dev: torch.device) -> torch.Tensor:
+    """100 Gaussian blobs of sigma 0.01 with uniform centres, wrapped into the unit cube."""
+    g = torch.Generator(device=dev).manual_seed(1)
+    centres = torch.rand((100, 3), generator=g, device=dev)
+    which = torch.randint(0, 100, (n,), generator=g, device=dev)
+    p = centres[which] + 0.01 * torch.randn((n, 3), generator=g, device=dev)
+    return E.wrap_points(p, 1.0)
 
 
 def pair_list_sums(index, q: torch.Tensor, r: float, w: torch.Tensor, per: dict, chunk: int) -> torch.Tensor:
@@ -389,8 +480,15 @@ def main() -> int:
                     help="--pairs-2d: the line of sight, the z axis or from --observer to each pair's midpoint")
     ap.add_argument("--observer", type=lambda t: tuple(float(v) for v in t.split(",")), default=None,
                     metavar="ox,oy,oz", help="--los midpoint: the observer (default 0.5,0.5,-3)")
+    ap.add_argument("--reach", choices=["either", "both"], default=None,
+                    help="time the two-sided search under this rule instead (self queries, k-th distances as radii)")
+    ap.add_argument("--dist", choices=["uniform", "clustered"], default="uniform", help="--reach: the point set")
     add_period_option(ap)
     a = ap.parse_args()
+    if a.reach is None and a.dist != "uniform":
+        ap.error("--dist belongs to --reach")
+    if a.reach is not None and (a.profile or a.pairs_2d is not None or a.radii != "scalar"):
+        ap.error("--reach is a mode of its own: not with --profile, --pairs-2d or --radii")
     if a.pairs_2d is None and (a.smu or a.skip_pair_list):
         ap.error("--smu and --skip-pair-list belong to --pairs-2d")
     if (a.los == "midpoint" and (a.pairs_2d is None or a.period is not None)) or \
@@ -412,6 +510,8 @@ def main() -> int:
     p = torch.rand((n, 3), generator=torch.Generator(device=dev).manual_seed(1), device=dev)
     q = torch.rand((nq, 3), generator=torch.Generator(device=dev).manual_seed(2), device=dev)
     r = (k / (n * 4.0 / 3.0 * math.pi)) ** (1.0 / 3.0)
+    if a.reach is not None:
+        return reach_bench(a, clustered_points(n, dev) if a.dist == "clustered" else p, per)
     if a.pairs_2d is not None:
         return pairs2d_bench(a, p, p if a.self_queries else q, per)
     if a.profile:
